@@ -7,8 +7,16 @@ document.  One step = one full reweave of the GPU's whole batch through the C
 ABI (cw_weave_lists, device memory): sorted ids, parents, weave order, rendered
 bits and counts per document.  Inputs are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line
+(value, ms_per_step, the workload).  --dump-outputs DIR also writes what the
+last timed step computed as DIR/<name>.npy.  --full adds everything else the
+line can carry, each in steps or host work of its own after the timed region:
+the CPU baselines, the sample check against the oracle (or --check: every
+document), the per-kernel and roofline figures, the refresh_caches and the
+PCIe-inclusive rates, config 3's pre-staged pass.
 
 Prints ONE JSON line on rank 0.
 """
@@ -83,7 +91,24 @@ def parse():
                     help="without --check: the last timed step's outputs of this many documents "
                          "(configs 1/2/5; collections for config 4) spread over the batch are "
                          "compared with the oracle after timing (0: off)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure as well: CPU baselines, the "
+                         "check against the oracle, per-kernel and roofline figures, "
+                         "refresh_caches, the PCIe-inclusive and pre-staged passes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="configs 1/2/5: write the last timed step's outputs as DIR/<name>.npy "
+                         "(float32/float64; a seeded sample of the per-node arrays when they "
+                         "are larger than the 64 MB the files may take)")
+    a = ap.parse_args()
+    if a.check and not a.full:
+        ap.error("--check compares with the oracle: it needs --full")
+    if a.dump_outputs and (a.config in (3, 4) or (a.config == 5 and (a.gpus > 1 or a.dist))):
+        ap.error("--dump-outputs: only the resident list paths (configs 1, 2 and 5 on their "
+                 "own GPU) write their outputs")
+    if not a.full:  # a plain run: the headline figure alone
+        a.no_cpu = a.no_refresh = a.no_h2d = a.no_prestaged = True
+        a.check_docs = 0
+    return a
 
 
 def launch_ranks(a) -> int:
@@ -177,6 +202,51 @@ def check_snapshot_lists(off, idk, ck, kd, snap):
               np.array_equal(gvis, vis[a:b]) and gvc == int(vis[a:b].sum()))
         bad += 0 if ok else 1
     return len(snap), bad
+
+
+DUMP_NODE_BYTES = 48_000_000  # of --dump-outputs' 64 MB: weave_perm.npy + visible.npy
+
+
+def dump_sample(off, dtype_bytes):
+    """Node positions whose weave_perm and visible bit --dump-outputs writes:
+    every node if that fits DUMP_NODE_BYTES, else whole documents picked by a
+    fixed seed (in batch order), else (one document too large) positions of
+    that seed.  The same batch gives the same sample in every run."""
+    N, D = int(off[-1]), len(off) - 1
+    budget = DUMP_NODE_BYTES // (dtype_bytes + 4)
+    if N <= budget:
+        return np.arange(N, dtype=np.int64)
+    rng = np.random.default_rng(0)
+    sizes = np.diff(off.astype(np.int64))
+    if D > 1 and int(sizes.max()) <= budget:
+        order = rng.permutation(D)
+        k = int(np.searchsorted(np.cumsum(sizes[order]), budget, side="right"))
+        docs = np.sort(order[:k])
+        return np.concatenate([np.arange(int(off[d]), int(off[d + 1]), dtype=np.int64)
+                               for d in docs])
+    return np.unique(rng.integers(0, N, budget, dtype=np.int64))
+
+
+def dump_lists(path, rank, off, torch, dev, perm, bits, vcount, max_ts, status):
+    """--dump-outputs: what cw_weave_lists left in the caller's arrays in the
+    last timed step, as <name>.npy (rank 0; <name>_rank<r>.npy on the others):
+    visible_count, max_ts and status of every document (float64), and
+    weave_perm (float32 while a document's positions fit 24 bits, else
+    float64) and the visible bit (0/1, float32) at dump_sample's positions."""
+    os.makedirs(path, exist_ok=True)
+    big = int(np.diff(off.astype(np.int64)).max()) > 1 << 24
+    pdt = np.float64 if big else np.float32
+    sel = dump_sample(off, np.dtype(pdt).itemsize)
+    idx = torch.from_numpy(sel).to(dev)
+    g_perm = perm[idx].cpu().numpy().view(np.uint32)
+    g_vis = ((bits[idx >> 5] >> (idx & 31).to(torch.int32)) & 1).cpu().numpy()
+    arrays = {"weave_perm": g_perm.astype(pdt), "visible": g_vis.astype(np.float32),
+              "visible_count": vcount.cpu().numpy().view(np.uint32).astype(np.float64),
+              "max_ts": max_ts.cpu().numpy().astype(np.float64),
+              "status": status.cpu().numpy().view(np.uint32).astype(np.float64)}
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), arr)
 
 
 def check_maps(off, idk, ck, ci, kd, o, S, colls=None):
@@ -869,19 +939,20 @@ def main():
     if int(status.max().item()) != 0:
         raise SystemExit(f"rank {rank}: documents out of domain: status max {status.max().item()}")
 
-    # the dominant kernel: one step with events around every launch
-    w.reset_kernel_stats()
-    w.set_profiling(True)
-    step()
-    torch.cuda.synchronize()
-    w.set_profiling(False)
-    dom = max(w.kernel_stats().items(), key=lambda kv: kv[1][1])[0]
-    # timed region: HIP events on the launch stream around the dominant
-    # kernel's launches only (two events a launch: per-kernel events on every
-    # launch cost a sub-millisecond one-list step a third of its time)
-    w.reset_kernel_stats()
-    w.set_profile_only(dom)
-    w.set_profiling(True)
+    if a.full:
+        # the dominant kernel: one step with events around every launch
+        w.reset_kernel_stats()
+        w.set_profiling(True)
+        step()
+        torch.cuda.synchronize()
+        w.set_profiling(False)
+        dom = max(w.kernel_stats().items(), key=lambda kv: kv[1][1])[0]
+        # timed region: HIP events on the launch stream around the dominant
+        # kernel's launches only (two events a launch: per-kernel events on every
+        # launch cost a sub-millisecond one-list step a third of its time)
+        w.reset_kernel_stats()
+        w.set_profile_only(dom)
+        w.set_profiling(True)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -892,6 +963,36 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dt_max = shard.reduce_max_time(dt, dist, dev) if world > 1 else dt
+    total_nodes = N * world * a.steps
+    value = total_nodes / dt_max
+    b_io = b_io_bytes(4 if k32 else 8, 4)
+    line = {
+        "metric": "nodes woven/sec (whole node) + % of HBM roofline at 1/2/4/8 MI355X",
+        "value": value, "unit": "nodes/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": dt_max / a.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": workload,
+                   "docs_per_gpu": D, "nodes_per_doc": spec.doc_size,
+                   "nodes_per_gpu": N, "sites": spec.n_sites, "p_hide": spec.p_hide,
+                   "p_show": spec.p_show, "p_conj": spec.p_conj,
+                   "key_bits": layout.key_bits,
+                   "key_words": "u32 (cw_weave_lists_k32)" if k32 else "u64 (cw_weave_lists)",
+                   "parallelism": (f"replicas x{world}" if a.config in (1, 5)
+                                   else f"docs sharded x{world}")},
+    }
+    # the last timed step's outputs, copied out before anything else runs
+    if a.dump_outputs:
+        dump_lists(a.dump_outputs, rank, off, torch, dev, perm, bits, vcount, max_ts, status)
+    if not a.full:  # a plain run ends here
+        if rank == 0:
+            line["frac_step_io"] = value * b_io / 1e9 / HBM_PEAK_GBS / world
+            line["gen_s"] = t_gen
+            print(json.dumps(line), flush=True)
+        w.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     w.set_profiling(False)
     w.set_profile_only(None)
     stats_dom = w.kernel_stats()
@@ -919,9 +1020,6 @@ def main():
     w.set_profiling(False)
     stats = w.kernel_stats()
 
-    dt_max = shard.reduce_max_time(dt, dist, dev) if world > 1 else dt
-    total_nodes = N * world * a.steps
-    value = total_nodes / dt_max
     # the full reconstitute path (s/refresh-caches, shared.cljc:259-266: spin ->
     # refresh-ts -> weave-fn): the same steps with the yarns (yarn_perm, the id
     # order partitioned by site) asked for as well; `value` stays the weave's
@@ -1021,7 +1119,6 @@ def main():
     # with u32).  The fused per-document kernel does the whole weave, so its
     # algorithmic bytes are B_io x the nodes of a launch; its own scratch
     # handoffs (achieved_kernel_scratch) are not algorithmic bytes.
-    b_io = b_io_bytes(4 if k32 else 8, 4)
     whole = name == "weave"
     achieved = achieved_gbs(N * b_io, launches, ms) if whole else achieved_gbs(by / launches, launches, ms)
     kernel_ms_total = sum(v[1] for v in stats.values())
@@ -1041,19 +1138,7 @@ def main():
             with heartbeat("cpu_baseline"):
                 cpu = (cpu_baseline_prefix(*_k64(idk, ck), kd, 100_000) if a.config == 5 else
                        cpu_baseline(spec, a.cpu_seconds, max_docs=1 if a.config == 1 else 64))
-        line = {
-            "metric": "nodes woven/sec (whole node) + % of HBM roofline at 1/2/4/8 MI355X",
-            "value": value, "unit": "nodes/s", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": dt_max / a.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": workload,
-                       "docs_per_gpu": D, "nodes_per_doc": spec.doc_size,
-                       "nodes_per_gpu": N, "sites": spec.n_sites, "p_hide": spec.p_hide,
-                       "p_show": spec.p_show, "p_conj": spec.p_conj,
-                       "key_bits": layout.key_bits,
-                       "key_words": "u32 (cw_weave_lists_k32)" if k32 else "u64 (cw_weave_lists)",
-                       "parallelism": (f"replicas x{world}" if a.config in (1, 5)
-                                       else f"docs sharded x{world}")},
+        line.update({
             "roofline": {"bound": "hbm", "kernel": name, "achieved": achieved,
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "frac_io": achieved / HBM_PEAK_GBS if whole else None,
@@ -1079,7 +1164,7 @@ def main():
             # device memory in use after the timed steps (inputs, outputs and the
             # library's scratch): the config-5 sizing
             "hbm_used_gib": round((lambda f, t: (t - f) / 2**30)(*torch.cuda.mem_get_info(dev)), 2),
-        }
+        })
         if cpu:
             line["speedup_vs_cpu_baseline"] = value / cpu["value"]
         if check:

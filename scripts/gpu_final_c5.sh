@@ -5,13 +5,14 @@
 #                                         (2^26 nodes), the config-5 and config-1 lines
 #   bash scripts/gpu_final_c5.sh full     the same at BASELINE's 2,000,000,001 nodes
 #                                         (input generated once into /tmp/c5cache)
-# Each extends gpurun_out/pmc_traffic.json (and profiles/ on the box) with its workload.
+# Each extends $OUT_DIR/pmc_traffic.json (default out/; and profiles/) with its workload.
 set -e
 R="${GRAFT_REPO_ROOT:-$PWD}"
 cd "$R"
-O=gpurun_out/c5
+T="${OUT_DIR:-out}"
+O=$T/c5
 mkdir -p $O
-cp profiles/pmc_traffic.json gpurun_out/pmc_traffic.json
+cp profiles/pmc_traffic.json $T/pmc_traffic.json
 pmc() {  # $1 = dir, $2 = seconds, rest = bench args
   local dir=$1 lim=$2; shift 2
   mkdir -p "$R/$dir"
@@ -26,20 +27,20 @@ case "$1" in
   scaled)
     pmc $O/pmc26 300 --config 5
     python scripts/pmc_summary.py $O/pmc26 > $O/pmc_table_config5.txt
-    python scripts/pmc_traffic.py $O/pmc26 gpurun_out/pmc_traffic.json --workload config5
+    python scripts/pmc_traffic.py $O/pmc26 $T/pmc_traffic.json --workload config5
     rm -rf $O/pmc26/pmc_*
-    cp gpurun_out/pmc_traffic.json profiles/pmc_traffic.json  # (the lines below read it)
-    timeout -k 10 300 python bench.py --config 5 > $O/c5.json 2> $O/c5.err
-    timeout -k 10 300 python bench.py --config 1 > $O/c1.json 2> $O/c1.err
+    cp $T/pmc_traffic.json profiles/pmc_traffic.json  # (the lines below read it)
+    timeout -k 10 300 python bench.py --full --config 5 > $O/c5.json 2> $O/c5.err
+    timeout -k 10 300 python bench.py --full --config 1 > $O/c1.json 2> $O/c1.err
     echo "scaled ok" ;;
   full)
     pmc $O/pmcfull 900 --config 5 --giant 2000000001 --cache /tmp/c5cache
     python scripts/pmc_summary.py $O/pmcfull > $O/pmc_table_config5full.txt
-    python scripts/pmc_traffic.py $O/pmcfull gpurun_out/pmc_traffic.json --workload config5full
+    python scripts/pmc_traffic.py $O/pmcfull $T/pmc_traffic.json --workload config5full
     rm -rf $O/pmcfull/pmc_*
-    cp gpurun_out/pmc_traffic.json profiles/pmc_traffic.json  # (the lines below read it)
-    timeout -k 10 600 python bench.py --config 5 --giant 2000000001 --cache /tmp/c5cache --steps 2 --warmup 1 > $O/c5full.json 2> $O/c5full.err
-    timeout -k 10 300 python bench.py --config 5 > $O/c5.json 2> $O/c5.err
+    cp $T/pmc_traffic.json profiles/pmc_traffic.json  # (the lines below read it)
+    timeout -k 10 600 python bench.py --full --config 5 --giant 2000000001 --cache /tmp/c5cache --steps 2 --warmup 1 > $O/c5full.json 2> $O/c5full.err
+    timeout -k 10 300 python bench.py --full --config 5 > $O/c5.json 2> $O/c5.err
     echo "full ok" ;;
   *) echo "usage: $0 scaled|full"; exit 2 ;;
 esac

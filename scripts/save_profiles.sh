@@ -1,9 +1,9 @@
 #!/bin/bash
-# Copy a gpu_measure.sh run's summaries from gpurun_out/ into profiles/ (tracked):
+# Copy a gpu_measure.sh run's summaries from $OUT_DIR (default out/) into profiles/ (tracked):
 #   bash scripts/save_profiles.sh r03_v1
 set -e
 tag="$1"; [ -n "$tag" ] || { echo "usage: $0 TAG"; exit 2; }
-O=gpurun_out
+O="${OUT_DIR:-out}"
 [ -f $O/bench.log ] && grep '^{' $O/bench.log | tail -1 > profiles/${tag}_bench.json
 ks=$(find $O/prof -name '*kernel_stats.csv' | head -1)
 [ -n "$ks" ] && cp "$ks" profiles/${tag}_kernel_stats.csv

@@ -21,9 +21,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(*args, timeout=300):
+    """One `bench.py --full` run (the CPU baseline, --check and the roofline
+    figures are behind --full) -> its JSON line."""
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), *args],
+    p = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--full", *args],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
