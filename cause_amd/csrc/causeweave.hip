@@ -1356,12 +1356,6 @@ __host__ __device__ inline uint32_t front_lds_bytes(uint32_t nmax, uint32_t sg) 
 // null (the tree reads the class bitmaps).
 // U1 / U2 / U3: items a thread keeps in flight in the directory, rank and
 // input-index passes (the fused kernel's front end is latency-bound: CW_FRONT_U)
-// Where the fused front end writes the yarns' site bytes (round 6 A/B).
-#ifndef CW_SITE8_RANKPASS
-#define CW_SITE8_RANKPASS 0
-#endif
-constexpr bool SITE8_PASS1 = CW_SITE8_RANKPASS == 0;
-
 template <int NT, typename PT = uint32_t, typename VT = uint32_t, uint32_t U1 = 4, uint32_t U2 = 4,
           uint32_t U3 = 4>
 __device__ __forceinline__ bool front_doc(
@@ -1417,9 +1411,8 @@ __device__ __forceinline__ bool front_doc(
       if (i0 + u * NT >= n) continue;
       mx = max(mx, x[u]);
       // the site of every input for the yarns (k_yarn_doc): one coalesced byte,
-      // written in this pass, whose loads are few and early (CW_SITE8_RANKPASS = 1
-      // at build time: in the rank pass, as round 5 had it)
-      if (SITE8_PASS1 && site8) lane_at(site8 + base, i0 + u * NT) = (uint8_t)((x[u] >> site_shift) & site_mask);
+      // written in this pass, whose loads are few and early
+      if (site8) lane_at(site8 + base, i0 + u * NT) = (uint8_t)((x[u] >> site_shift) & site_mask);
       if (x[u] >= lim) {
         far = true;
         continue;
@@ -1517,8 +1510,6 @@ __device__ __forceinline__ bool front_doc(
         if (cls & 2) atomicOr(&clsB[r >> 5], 1u << (r & 31));
       }
       lane_at(rankD, i) = (uint16_t)min(r, 0xFFFFu);
-      // the site of every input for the yarns (k_yarn_doc): one coalesced byte
-      if (!SITE8_PASS1 && site8) lane_at(site8 + base, i) = (uint8_t)((k[u] >> site_shift) & site_mask);
     }
   }
   if (st) atomicOr(&bst, st);
@@ -1958,13 +1949,6 @@ __host__ __device__ inline uint32_t tree_l_lds_bytes(uint32_t nmax) {
   return ((nmax + 31) / 32) * 8 + ((nmax + 1) / 2) * 4;  // two bitmaps + u16 table
 }
 
-// Sweep 2 of the tree without the barrier between pointer jumping and the
-// write-out (round 6; CW_S2_JUMP_BARRIER=1 at build time restores it for A/Bs).
-#ifndef CW_S2_JUMP_BARRIER
-#define CW_S2_JUMP_BARRIER 0
-#endif
-constexpr bool S2_JUMP_NOBAR = CW_S2_JUMP_BARRIER == 0;
-
 // MODE 4 (the one built; round 3's A/B variants 0-3 lost and are gone): a
 // group whose parent lies in the tile (69% of config-2 nodes) keeps its list
 // head in a direct table indexed by (class, parent - tile start): one exchange
@@ -2339,7 +2323,6 @@ __device__ __forceinline__ void tree_l_doc(
     // (no barrier here: a lane writes out only the entries it resolved itself,
     // into tab and the links, which no jumping lane reads; the barrier after
     // the writes keeps the next tile's T and its reads of tab apart -- round 6)
-    if (!S2_JUMP_NOBAR) __syncthreads();
     stamp(6);
 #pragma unroll
     for (uint32_t k = 0; k < IT; k++) {
@@ -4361,9 +4344,16 @@ struct cw_ctx {
   } tab;
   bool tab_on_device = false;
   bool last_giant = false;
-  // launch geometry (fixed at cw_ctx_create)
-  uint32_t tb = 1024, walk_threads = 1024, walk_span = 1024, giant_log2cap = 5, glocal = 1, glocal_min = 1u << 20, min_log2k = 5,
-           max_digit = MAX_DIGIT, min_log2cap = 4;
+  // These initialisers are the only statement of a default: cw_ctx_create
+  // overwrites a field whose CW_* variable is set, and nothing else.
+  // launch geometry (round 5: the A/B knobs CW_TB, CW_WALK_THREADS, CW_WALK_SPAN,
+  // CW_LOG2K, CW_LOG2CAP and CW_MAX_DIGIT are gone, their measured values stay):
+  // one walker per thread (span == threads: a dynamic walker queue per block was slower)
+  uint32_t tb = 1024, walk_threads = 512, walk_span = 512, min_log2k = MIN_LOG2K, min_log2cap = 4,
+           max_digit = MAX_DIGIT;
+  uint32_t giant_log2cap = 5;      // CW_GIANT_LOG2CAP: walk slot entries of a giant document
+  uint32_t glocal_min = 1u << 20;  // CW_GLOCAL_MIN: a giant tree of this many nodes links siblings
+                                   // tile by tile (k_glocal) and sorts only cross-tile children
   // rank-directory front end (CW_FRONT, CW_FRONT_SLOT bytes per document)
   uint32_t front = 1, front_slot_groups = 4096, front_min_avg = 1024;
   uint32_t *pin_small = nullptr;  // pinned 16-byte readback
@@ -4371,7 +4361,6 @@ struct cw_ctx {
   uint32_t tree_l = 2048;          // CW_TREE_L: k_tree_l (tables in LDS) when the largest document fits: its tile (2048 or 1024; 0 = k_tree)
   uint32_t gdir = 32;              // CW_GDIR: MiB of global rank directory a giant document may use
   uint32_t gjoin = 1;              // CW_GJOIN: the giant path joins through a directory of its sorted ids
-  uint32_t id_payload = 1;         // CW_ID_PAYLOAD: the id sort carries cause | kind to rank order (round 6)
   uint32_t map_small = 1;          // CW_MAP_SMALL: one wave per key weave of <= 64 nodes
   uint32_t pack_sort = 1;          // CW_PACK_SORT: in-LDS sort of packs of small documents
   uint32_t giant_min = 1u << 16;   // CW_GIANT_MIN: a one-document batch this large uses the giant tree
@@ -4383,13 +4372,7 @@ struct cw_ctx {
   uint32_t giant_log2k = 4;        // CW_GIANT_LOG2K: least splitter block of a giant document
   uint32_t fused = 1;              // CW_FUSED: front end + tree + tour in one kernel (k_weave_doc)
   bool x_hint = true;              // the last list weave may have flagged documents (exact.hip)
-  uint32_t onesweep = 4;           // CW_ONESWEEP: one-array sorts by the one-sweep passes
-                                   // (tiles of 4,096 keys x 512 threads, 8,192 x 1,024,
-                                   // 8,192 x 512: 1-3 in one look-back chain, 4-6 in
-                                   // OS_RANGES chains; 0: histogram-scan-scatter)
   uint32_t n_cu = 256;             // compute units of the device (histogram grid)
-  uint32_t os_exp = 0;             // CW_OS_EXP: onesweep timing experiments (wrong results)
-  uint32_t onesweep_min = 1u << 16;  // CW_ONESWEEP_MIN: ... for arrays of at least this many keys
   const void *os_lb = nullptr;     // onesweep.hip's look-back words: buffer, size, last epoch
   size_t os_lb_words = 0;
   uint32_t os_epoch = 0;
@@ -4741,94 +4724,72 @@ struct OsPayloadBufs {
 };
 
 // One array (one document, or rt's one list): the one-sweep passes
-// (onesweep.hip) -- one histogram launch for every pass, one scan launch, one
-// launch a pass.  Same contract as radix_sort.
+// (onesweep.hip) -- a histogram, a scan and a scatter launch a pass.  Same
+// contract as radix_sort.
 template <typename K>
 int onesweep_sort(cw_ctx *c, const char *tag, const K *kin, const uint32_t *vin, K *kA, uint32_t *vA,
                   K *kB, uint32_t *vB, uint32_t bits, uint32_t shift0, uint32_t N, K **kout,
                   uint32_t **vout, uint32_t *inv, uint32_t *vfinal, OsPayloadBufs *plb = nullptr) {
-  const uint32_t geom = c->onesweep;
-  // 1-3 one chain: 512 x 8, 1024 x 8, 512 x 16 keys a tile; 4-6 the same in
-  // OS_RANGES chains (4 = 1024 x 8, 5 = 512 x 8, 6 = 512 x 16)
-  const uint32_t shape = geom == 4 ? 2 : geom == 5 ? 1 : geom == 6 ? 3 : geom;
-  const uint32_t TS = shape == 1 ? 4096 : 8192;
-  const bool ranged = geom > 3;
-  OsDigits dg{};
-  dg.passes = (bits + OS_MAX_BITS - 1) / OS_MAX_BITS;
-  if (dg.passes > OS_MAX_PASSES) return fail(c, "onesweep: %u key bits", bits);
-  for (uint32_t p = 0, sh = shift0; p < dg.passes; p++) {
-    // the wider digits last, as radix_sort
-    dg.bits[p] = bits / dg.passes + (p >= dg.passes - bits % dg.passes ? 1u : 0u);
-    dg.shift[p] = sh;
-    sh += dg.bits[p];
-  }
+  constexpr uint32_t NT = 1024, TS = NT * 8;  // k_os_pass: threads, keys a tile
+  const uint32_t passes = (bits + OS_MAX_BITS - 1) / OS_MAX_BITS;
+  if (passes > OS_MAX_PASSES) return fail(c, "onesweep: %u key bits", bits);
   const uint32_t T = (N + TS - 1) / TS;
-  const uint32_t nr = ranged ? OS_RANGES : 1u;
-  const uint32_t Tr = (T + nr - 1) / nr;  // tiles a range
-  const uint32_t rlen = ranged ? Tr * TS : 0xFFFFFFFFu;
-  const size_t hist_words = (size_t)OS_MAX_PASSES * OS_RANGES * OS_MAX_BINS;
+  const uint32_t Tr = (T + OS_RANGES - 1) / OS_RANGES;  // tiles a range
+  const uint32_t rlen = Tr * TS;
+  // per pass and range: digit counts, bucket bases; per pass: the ranges' tickets
+  const size_t pass_words = (size_t)OS_RANGES * OS_MAX_BINS, hist_words = OS_MAX_PASSES * pass_words;
   uint32_t *hist = scratch_t<uint32_t>(c, "os_hist", 2 * hist_words + OS_MAX_PASSES * OS_RANGES);
-  const size_t lb_words = (size_t)Tr * nr * OS_MAX_BINS;
+  const size_t lb_words = (size_t)Tr * OS_RANGES * OS_MAX_BINS;
   unsigned long long *lb = scratch_t<unsigned long long>(c, "os_lb", lb_words);
   if (!hist || !lb) return fail(c, "out of device memory (onesweep)");
   uint32_t *base = hist + hist_words, *ticket = base + hist_words;
   // look-back words: cleared when the buffer is new or the 16-bit epoch wraps
-  if (lb != c->os_lb || lb_words > c->os_lb_words || c->os_epoch + dg.passes > 0xFFFFu) {
+  if (lb != c->os_lb || lb_words > c->os_lb_words || c->os_epoch + passes > 0xFFFFu) {
     HIPCHK(c, hipMemsetAsync(lb, 0, c->bufs["os_lb"].bytes, c->stream));
     c->os_lb = lb;
     c->os_lb_words = c->bufs["os_lb"].bytes / 8;
     c->os_epoch = 0;
   }
   HIPCHK(c, hipMemsetAsync(hist, 0, hist_words * 4, c->stream));
-  if (ranged) HIPCHK(c, hipMemsetAsync(ticket, 0, OS_MAX_PASSES * OS_RANGES * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(ticket, 0, OS_MAX_PASSES * OS_RANGES * 4, c->stream));
   char nm[48], nm_scan[48], nm_hist[48];
   snprintf(nm, sizeof nm, "%s_scatter", tag);
   snprintf(nm_scan, sizeof nm_scan, "%s_scan", tag);
   snprintf(nm_hist, sizeof nm_hist, "%s_hist", tag);
-  // the digit counts of a pass's input (every pass at once when there is one
-  // range: the counts do not depend on the order), then the bucket bases
-  auto count = [&](const K *keys, uint32_t p0, uint32_t np) -> int {
-    OsDigits d = dg;
-    d.passes = np;
-    for (uint32_t q = 0; q < np; q++) {
-      d.shift[q] = dg.shift[p0 + q];
-      d.bits[q] = dg.bits[p0 + q];
-    }
-    uint32_t *hp = hist + (size_t)p0 * OS_RANGES * OS_MAX_BINS;
-    {
-      Launch L(c, nm_hist, (double)N * sizeof(K));
-      const uint32_t span = 256 * OS_HIST_ITEMS;
-      const uint32_t G = std::max(nr, std::min(c->n_cu * 4, (N + span - 1) / span) / nr * nr);
-      hipLaunchKernelGGL(k_os_hist<K>, dim3(G), dim3(256), (size_t)4 * np * OS_MAX_BINS * 4, c->stream,
-                         keys, N, d, rlen, nr, hp);
-    }
-    if (check_launch(c, nm_hist)) return -1;
-    {
-      Launch L(c, nm_scan, (double)np * OS_RANGES * OS_MAX_BINS * 8);
-      hipLaunchKernelGGL(k_os_scan, dim3(np), dim3(OS_MAX_BINS), 0, c->stream, hp, d,
-                         base + (size_t)p0 * OS_RANGES * OS_MAX_BINS);
-    }
-    return check_launch(c, nm_scan);
-  };
-  if (!ranged && count(kin, 0, dg.passes)) return -1;
+  // the payload rides in a u64 key's spare bits, through passes that write keys
+  const bool pl_fits = plb && sizeof(K) == 8 && shift0 == 0 && bits <= OS_PL_MAX_BITS;
   const K *ki = kin;
   const uint32_t *vi = vin;
   K *ko = kA;
   uint32_t *vo = vA;
-  for (uint32_t p = 0; p < dg.passes; p++) {
-    const bool last = p + 1 == dg.passes;
+  for (uint32_t p = 0, shift = shift0; p < passes; p++) {
+    // the wider digits last, as radix_sort
+    const uint32_t dbits = bits / passes + (p >= passes - bits % passes ? 1u : 0u);
+    const bool last = p + 1 == passes;
     if (last && vfinal) {
       ko = nullptr;
       vo = vfinal;
     }
-    // ranged: each pass counts its own input by range (a range's counts depend
-    // on which keys the previous pass put there)
-    if (ranged && count(ki, p, 1)) return -1;
+    // the digit counts of this pass's input by range (a range's counts depend
+    // on which keys the previous pass put there), then the bucket bases
+    uint32_t *const hp = hist + p * pass_words, *const bp = base + p * pass_words;
+    {
+      Launch L(c, nm_hist, (double)N * sizeof(K));
+      const uint32_t span = 256 * OS_HIST_ITEMS;
+      const uint32_t G =
+          std::max(OS_RANGES, std::min(c->n_cu * 4, (N + span - 1) / span) / OS_RANGES * OS_RANGES);
+      hipLaunchKernelGGL(k_os_hist<K>, dim3(G), dim3(256), 0, c->stream, ki, N, shift, dbits, rlen, hp);
+    }
+    if (check_launch(c, nm_hist)) return -1;
+    {
+      Launch L(c, nm_scan, (double)OS_RANGES * OS_MAX_BINS * 8);
+      hipLaunchKernelGGL(k_os_scan, dim3(1), dim3(OS_MAX_BINS), 0, c->stream, hp, 1u << dbits, bp);
+    }
+    if (check_launch(c, nm_scan)) return -1;
     const uint32_t ep = ++c->os_epoch;
-    const size_t pw = (size_t)p * OS_RANGES * OS_MAX_BINS;
     // the payload: packed from its source in pass 0, then the half buffers in turn
     OsPayload pl{};
-    const bool carry = plb && sizeof(K) == 8 && shape == 2 && shift0 == 0 && bits <= OS_PL_MAX_BITS && ko;
+    const bool carry = pl_fits && ko;
     if (carry) {
       pl.cause = p == 0 ? plb->cause : nullptr;
       pl.kind = p == 0 ? plb->kind : nullptr;
@@ -4841,26 +4802,22 @@ int onesweep_sort(cw_ctx *c, const char *tag, const K *kin, const uint32_t *vin,
     {
       Launch L(c, nm, (double)N * ((ko ? 2 : 1) * sizeof(K) + (vi ? 8 : 4) + (last && inv ? 4 : 0) +
                                    (carry ? (p == 0 ? 9 : 4) + 4 + (last ? 4 : 0) : 0)));
-      auto launch = [&](auto kern, uint32_t nt) {
-        hipLaunchKernelGGL(kern, dim3(Tr * nr), dim3(nt), 0, c->stream, ki, vi, ko, vo,
-                           last ? inv : nullptr, N, dg.shift[p], dg.bits[p], base + pw, lb, ep, c->os_exp,
-                           Tr, ranged ? ticket + p * OS_RANGES : nullptr, pl);
+      auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(Tr * OS_RANGES), dim3(NT), 0, c->stream, ki, vi, ko, vo,
+                           last ? inv : nullptr, N, shift, dbits, bp, lb, ep, Tr, ticket + p * OS_RANGES, pl);
       };
-      if (shape == 1) {
-        launch(k_os_pass<K, 512, 8>, 512);
-      } else if (shape == 3) {
-        launch(k_os_pass<K, 512, 16>, 512);
-      } else if (!carry) {
-        launch(k_os_pass<K, 1024, 8>, 1024);
+      if (!carry) {
+        launch(k_os_pass<K, NT, 8>);
       } else if constexpr (sizeof(K) == 8) {  // (the payload's role: a kernel each)
         const int m = 1 | (p == 0 ? 2 : 0) | (last ? 4 : 0);
-        if (m == 1) launch(k_os_pass<K, 1024, 8, 1>, 1024);
-        else if (m == 3) launch(k_os_pass<K, 1024, 8, 3>, 1024);
-        else if (m == 5) launch(k_os_pass<K, 1024, 8, 5>, 1024);
-        else launch(k_os_pass<K, 1024, 8, 7>, 1024);
+        if (m == 1) launch(k_os_pass<K, NT, 8, 1>);
+        else if (m == 3) launch(k_os_pass<K, NT, 8, 3>);
+        else if (m == 5) launch(k_os_pass<K, NT, 8, 5>);
+        else launch(k_os_pass<K, NT, 8, 7>);
       }
     }
     if (check_launch(c, nm)) return -1;
+    shift += dbits;
     ki = ko;
     vi = vo;
     ko = (ko == kA) ? kB : kA;
@@ -4868,10 +4825,7 @@ int onesweep_sort(cw_ctx *c, const char *tag, const K *kin, const uint32_t *vin,
   }
   *kout = const_cast<K *>(ki);
   *vout = const_cast<uint32_t *>(vi);
-  if (plb) {
-    const bool carried = sizeof(K) == 8 && shape == 2 && shift0 == 0 && bits <= OS_PL_MAX_BITS && !vfinal;
-    plb->lo_out = carried ? plb->lo[(dg.passes + 1) & 1] : nullptr;
-  }
+  if (plb) plb->lo_out = pl_fits && !vfinal ? plb->lo[(passes + 1) & 1] : nullptr;
   return 0;
 }
 
@@ -4912,8 +4866,8 @@ int radix_sort(cw_ctx *c, const char *tag, const K *kin, const uint32_t *vin, K 
     return 0;
   }
   // one array (config 5's ids, the giant tree's cross-tile children): the
-  // one-sweep passes (CW_ONESWEEP; 0 = the histogram-scan-scatter passes below)
-  if (c->onesweep && tt.D == 1 && N >= c->onesweep_min)
+  // one-sweep passes; a smaller one takes the histogram-scan-scatter passes below
+  if (tt.D == 1 && N >= OS_MIN_KEYS)
     return onesweep_sort<K>(c, tag, kin, vin, kA, vA, kB, vB, bits, shift0, N, kout, vout, inv, vfinal, plb);
   const uint32_t maxd = std::min<uint32_t>(c->max_digit, MAX_DIGIT);
   const int passes = (int)((bits + maxd - 1) / maxd);
@@ -4941,21 +4895,9 @@ int radix_sort(cw_ctx *c, const char *tag, const K *kin, const uint32_t *vin, K 
     }
     if (check_launch(c, nm)) return -1;
     snprintf(nm, sizeof nm, "%s_scan", tag);
-    if (D == 1 && tt.T > GSCAN_CHUNK) {
-      // one document of many tiles: chunked scan over all workgroups (up to
-      // one chunk of tiles, the one-workgroup scan is a single launch instead
-      // of four)
-      const uint32_t nc = (tt.T + GSCAN_CHUNK - 1) / GSCAN_CHUNK;
-      uint32_t *cs = scratch_t<uint32_t>(c, "gscan_cs", (size_t)nc * nb);
-      uint32_t *tot = scratch_t<uint32_t>(c, "gscan_tot", nb);
-      if (!cs || !tot) return fail(c, "out of device memory (scan)");
-      Launch L(c, nm, (double)tt.T * nb * 12);
-      hipLaunchKernelGGL(k_gscan_colsum, dim3(nc), dim3(1024), 0, c->stream, hist, tt.T, nb, cs);
-      hipLaunchKernelGGL(k_gscan_chunks, dim3((nb + 1023) / 1024), dim3(1024), 0, c->stream, cs, nc,
-                         nb, tot);
-      hipLaunchKernelGGL(k_gscan_bins, dim3(1), dim3(1024), 0, c->stream, tot, nb, 0u);
-      hipLaunchKernelGGL(k_gscan_apply, dim3(nc), dim3(1024), 0, c->stream, hist, tt.T, nb, cs, tot);
-    } else {
+    {
+      // one workgroup a document (one document of >= OS_MIN_KEYS keys, the only
+      // one with many tiles, went to the one-sweep passes)
       Launch L(c, nm, (double)tt.T * nb * 8);
       hipLaunchKernelGGL(k_radix_scan, dim3(D), dim3(1024), 0, c->stream, hist,
                          tt.tile_first, tt.doc_off, dbits);
@@ -5081,7 +5023,7 @@ int weave_tail(cw_ctx *c, uint64_t D, uint32_t N, bool giant, const uint32_t *pa
     }
     if (!gkA || !gkB || !gvA || !gvB || !gk) return fail(c, "out of device memory (giant tree)");
     const dim3 GN((N + 255) / 256);
-    const bool glocal = c->glocal && N >= c->glocal_min;
+    const bool glocal = N >= c->glocal_min;
     const uint32_t TL = (N + GL_TILE - 1) / GL_TILE;
     uint32_t *tcnt = nullptr;
     if (glocal) {
@@ -5650,7 +5592,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
     const bool gd_join = is_giant(c, D, bt->doc_offsets) && c->gjoin && key_bits <= GD_MAX_BITS;
     OsPayloadBufs plb{};
     OsPayloadBufs *plp = nullptr;
-    if (gd_join && key_bits <= OS_PL_MAX_BITS && c->id_payload) {
+    if (gd_join && key_bits <= OS_PL_MAX_BITS) {
       plb.cause = cause_key;
       plb.kind = kind;
       plb.status = out->status;
@@ -7037,45 +6979,37 @@ int cw_ctx_create(int device, cw_ctx **out) {
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
       c->n_cu = (uint32_t)ncu;
   }
-  auto knob = [](const char *name, uint32_t dflt) {
-    const char *v = getenv(name);
-    return v ? (uint32_t)strtoul(v, nullptr, 0) : dflt;
+  // a field keeps its initialiser (cw_ctx) unless its variable is set
+  auto knob = [](const char *name, uint32_t &field) {
+    if (const char *v = getenv(name)) field = (uint32_t)strtoul(v, nullptr, 0);
   };
-  // launch geometry (round 5: the A/B knobs CW_TB, CW_WALK_THREADS, CW_WALK_SPAN,
-  // CW_LOG2K, CW_LOG2CAP and CW_MAX_DIGIT are gone, their measured values stay):
-  // one walker per thread (span == threads: a dynamic walker queue per block was slower)
-  c->tb = 1024;
-  c->walk_threads = 512;
-  c->walk_span = 512;
-  c->min_log2k = MIN_LOG2K;
-  c->min_log2cap = 4;
-  c->max_digit = MAX_DIGIT;
-  c->front = knob("CW_FRONT", 1);
-  c->tree_prof = knob("CW_TREE_PROF", 0);
-  c->tree_l = knob("CW_TREE_L", 2048);
-  c->gdir = knob("CW_GDIR", 32);
-  c->gjoin = knob("CW_GJOIN", 1);
-  c->id_payload = knob("CW_ID_PAYLOAD", 1);
-  c->glocal = knob("CW_GLOCAL", 1);
-  c->glocal_min = knob("CW_GLOCAL_MIN", 1u << 20);
-  c->map_small = knob("CW_MAP_SMALL", 1);
-  c->map_fused = knob("CW_MAP_FUSED", 1);
-  c->pack_sort = knob("CW_PACK_SORT", 1);
-  c->giant_min = knob("CW_GIANT_MIN", 1u << 16);
-  c->tour = knob("CW_TOUR", 1);
-  c->giant_docs_max = knob("CW_GIANT_DOCS", 32);
-  c->front_fused = knob("CW_FRONT_FUSED", 1);
-  c->tour_log2k = std::max(MIN_LOG2K, std::min(knob("CW_TOUR_LOG2K", 3), 12u));
-  c->giant_log2k = std::max(MIN_LOG2K, std::min(knob("CW_GIANT_LOG2K", 4), 12u));
-  c->giant_log2cap = std::max(2u, std::min(knob("CW_GIANT_LOG2CAP", 5), 12u));
-  c->fused = knob("CW_FUSED", 1);
-  c->xfold = knob("CW_XFOLD", 0);
-  c->x_round_cap = std::max(1u, knob("CW_X_ROUND_CAP", 48));
-  c->onesweep = std::min(knob("CW_ONESWEEP", 4), 6u);
-  c->onesweep_min = knob("CW_ONESWEEP_MIN", 1u << 16);
-  c->os_exp = knob("CW_OS_EXP", 0);
-  c->front_slot_groups = std::max(1u, std::min(knob("CW_FRONT_SLOT", 65536), 131072u) / 16);
-  c->front_min_avg = knob("CW_FRONT_MIN_AVG", 1024);
+  knob("CW_FRONT", c->front);
+  knob("CW_TREE_PROF", c->tree_prof);
+  knob("CW_TREE_L", c->tree_l);
+  knob("CW_GDIR", c->gdir);
+  knob("CW_GJOIN", c->gjoin);
+  knob("CW_GLOCAL_MIN", c->glocal_min);
+  knob("CW_MAP_SMALL", c->map_small);
+  knob("CW_MAP_FUSED", c->map_fused);
+  knob("CW_PACK_SORT", c->pack_sort);
+  knob("CW_GIANT_MIN", c->giant_min);
+  knob("CW_TOUR", c->tour);
+  knob("CW_GIANT_DOCS", c->giant_docs_max);
+  knob("CW_FRONT_FUSED", c->front_fused);
+  knob("CW_TOUR_LOG2K", c->tour_log2k);
+  c->tour_log2k = std::max(MIN_LOG2K, std::min(c->tour_log2k, 12u));
+  knob("CW_GIANT_LOG2K", c->giant_log2k);
+  c->giant_log2k = std::max(MIN_LOG2K, std::min(c->giant_log2k, 12u));
+  knob("CW_GIANT_LOG2CAP", c->giant_log2cap);
+  c->giant_log2cap = std::max(2u, std::min(c->giant_log2cap, 12u));
+  knob("CW_FUSED", c->fused);
+  knob("CW_XFOLD", c->xfold);
+  knob("CW_X_ROUND_CAP", c->x_round_cap);
+  c->x_round_cap = std::max(1u, c->x_round_cap);
+  uint32_t slot_bytes = c->front_slot_groups * 16;
+  knob("CW_FRONT_SLOT", slot_bytes);
+  c->front_slot_groups = std::max(1u, std::min(slot_bytes, 131072u) / 16);
+  knob("CW_FRONT_MIN_AVG", c->front_min_avg);
   *out = c;
   return 0;
 }

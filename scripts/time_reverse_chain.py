@@ -3,7 +3,7 @@ document with a 16,384-long reverse chain (rank r caused by rank r + 1), against
 the same document without the chain -- device-memory calls (inputs and outputs
 resident), min of 7 after a warm-up, for each knob set given.
 
-    python scripts/time_reverse_chain.py '[{}, {"CW_X2_JUMP1": "0"}]'
+    python scripts/time_reverse_chain.py '[{}, {"CW_XFOLD": "1"}]'
 
 One JSON line per variant: clean and chain ms, the ratio, the exact path's
 rounds (xins_round launches), all launches and the per-stage ms of one chain

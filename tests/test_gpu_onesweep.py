@@ -1,10 +1,12 @@
 """The one-sweep radix sort (cause_amd/csrc/onesweep.hip) behind cw_sort_keys /
 cw_sort_keys32 and every one-array sort of the library (config 5's id sort,
 list.cljc:28 / shared.cljc:128; the giant tree's cross-tile children):
-bit-exact against numpy's stable argsort, under every tile geometry, at sizes
-around the tile and chunk boundaries, with duplicates (stability), one
-bucket only (the longest look-back chains), nearly sorted keys and 64-bit
-keys (8 passes); and equal to the histogram-scan-scatter passes it replaces."""
+bit-exact against numpy's stable argsort, at sizes around the tile, range and
+threshold boundaries (2^16 keys: eight tiles, one a range; 2^16 + 1: empty
+ranges; just under 2^16: the histogram-scan-scatter passes a smaller array
+takes), with duplicates (stability), one bucket only (the longest look-back
+chains, across a range boundary), nearly sorted keys and 64-bit keys
+(8 passes); and again when the look-back words are reused across calls."""
 import numpy as np
 import pytest
 
@@ -38,23 +40,20 @@ def _check(w, k, bits):
     assert np.array_equal(io, order.astype(np.uint32))
 
 
-@pytest.mark.parametrize("geom", ["1", "2", "3", "4", "5", "6"])
-def test_onesweep_geometries(monkeypatch, geom):
-    monkeypatch.setenv("CW_ONESWEEP", geom)
+def test_onesweep_geometries():
     with abi.Weaver(0) as w:
-        for n, bits, kind in ((1 << 16, 17, "random"), ((1 << 16) + 1, 9, "few"),
+        for n, bits, kind in ((65_535, 17, "random"),  # (under OS_MIN_KEYS: hist-scan-scatter)
+                              (1 << 16, 17, "random"), ((1 << 16) + 1, 9, "few"),
                               (8 * 4096 * 3 + 17, 35, "random"), (8 * 8192 + 8191, 20, "one"),
                               (1_000_003, 33, "sorted"), (3_000_001, 35, "random"),
                               (200_000, 64, "random"), (123_457, 1, "few")):
             _check(w, _keys(kind, n, bits, n + bits), bits)
 
 
-def test_onesweep_equals_the_hist_scan_scatter_passes(monkeypatch):
+def test_onesweep_exact_across_repeated_calls():
     k = _keys("random", 2_500_000, 35, 5)
-    monkeypatch.setenv("CW_ONESWEEP", "0")
-    with abi.Weaver(0) as w:
-        ref = w.sort_keys(k, 35)
-    monkeypatch.delenv("CW_ONESWEEP")  # the default geometry
+    order = np.argsort(k, kind="stable")
+    ref = (k[order], order.astype(np.uint32))
     with abi.Weaver(0) as w:
         w.reset_kernel_stats()
         w.set_profiling(True)
@@ -65,16 +64,13 @@ def test_onesweep_equals_the_hist_scan_scatter_passes(monkeypatch):
             again = w.sort_keys(k, 35)
             assert np.array_equal(again[1], ref[1])
     assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1])
-    # 4 passes; the ranged default counts each pass's input (one histogram
-    # launch a pass), the single-chain geometries all passes at once
+    # 4 passes, each counting its own input (one histogram launch a pass)
     assert st["ksort_scatter"][0] == 4 and st["ksort_hist"][0] == 4
 
 
-@pytest.mark.parametrize("geom", ["1", "4", "5"])
-def test_onesweep_keys32(monkeypatch, geom):
+def test_onesweep_keys32():
     import torch
 
-    monkeypatch.setenv("CW_ONESWEEP", geom)
     rng = np.random.default_rng(3)
     with abi.Weaver(0) as w:
         for n, bits in ((70_000, 32), (1_000_001, 21)):
