@@ -183,6 +183,8 @@ def lib():
         L.cw_ctx_set_async.argtypes = [C.c_void_p, C.c_int]
         L.cw_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
         L.cw_ctx_set_profile_only.argtypes = [C.c_void_p, C.c_char_p]
+        if hasattr(L, "cw_ctx_set_option"):  # (a build from before it, named by CW_LIB for an A/B run)
+            L.cw_ctx_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
         L.cw_get_kernel_stats.argtypes = [C.c_void_p, C.POINTER(CwKernelStat), C.c_int]
         L.cw_reset_kernel_stats.argtypes = [C.c_void_p]
         L.cw_get_counter.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]
@@ -281,7 +283,8 @@ def _ptr(a):
 class Weaver:
     """A weave context on one HIP device (cw_ctx)."""
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, options: dict[str, int] | None = None):
+        """options: name -> value for cw_ctx_set_option (INTEGRATION.md lists them)."""
         self._L = lib()
         h = C.c_void_p()
         rc = self._L.cw_ctx_create(device, C.byref(h))
@@ -289,6 +292,8 @@ class Weaver:
             raise WeaveError(f"cw_ctx_create(device={device}) failed: no usable HIP device")
         self._h = h
         self.device = device
+        for name, value in (options or {}).items():
+            self.set_option(name, value)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -324,6 +329,10 @@ class Weaver:
         """Per-kernel events for this kernel stat name only (None: every kernel)."""
         self._check(self._L.cw_ctx_set_profile_only(self._h, kernel.encode() if kernel else None),
                     "set_profile_only")
+
+    def set_option(self, name: str, value: int):
+        """A path or geometry option, from the next call on (cw_ctx_set_option)."""
+        self._check(self._L.cw_ctx_set_option(self._h, name.encode(), int(value)), "set_option")
 
     def kernel_stats(self):
         n = self._L.cw_get_kernel_stats(self._h, None, 0)

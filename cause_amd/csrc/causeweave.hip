@@ -1368,7 +1368,7 @@ __device__ __forceinline__ bool front_doc(
     unsigned long long *__restrict__ tprof, uint32_t d, uint4 *sdir,
     uint8_t *__restrict__ site8 = nullptr, uint32_t site_shift = 0, uint32_t site_mask = 0) {
   unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
-  auto stamp = [&](int ph) {  // diagnostic phase times (CW_TREE_PROF)
+  auto stamp = [&](int ph) {  // diagnostic phase times (tree_prof)
     if (tprof) {
       const unsigned long long now = __builtin_amdgcn_s_memtime();
       if (ph >= 0) tacc[ph] += now - tlast;
@@ -1624,7 +1624,7 @@ __global__ __launch_bounds__(NT) void k_tree(
     uint32_t *__restrict__ status, unsigned long long *__restrict__ tprof,
     const uint32_t *__restrict__ kbm, const uint32_t *__restrict__ tile_first) {
   constexpr uint32_t IT = TILE_T / NT;
-  // diagnostic phase stamps (tprof != nullptr only under CW_TREE_PROF)
+  // diagnostic phase stamps (tprof != nullptr only under tree_prof)
   unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
   auto stamp = [&](int ph) {
     if (tprof) {
@@ -1965,7 +1965,7 @@ __device__ __forceinline__ void tree_l_doc(
     uint32_t *lds) {
   constexpr uint32_t IT = TILE_T / NT;
   unsigned long long tacc[16] = {}, tlast = 0;
-  auto stamp = [&](int ph) {  // diagnostic phase times (CW_TREE_PROF)
+  auto stamp = [&](int ph) {  // diagnostic phase times (tree_prof)
     if (PROF) {
       const unsigned long long now = __builtin_amdgcn_s_memtime();
       if (ph >= 0) tacc[ph] += now - tlast;
@@ -2704,7 +2704,7 @@ __global__ __launch_bounds__(1024) void k_walk(
     uint32_t *__restrict__ dyn_ctr, uint32_t *__restrict__ status, uint32_t walk_span,
     unsigned long long *__restrict__ wprof) {
   __shared__ uint32_t next_walker;
-  uint32_t n_steps = 0, n_pend = 0, n_hops = 0;  // (wprof: CW_TREE_PROF diagnostics)
+  uint32_t n_steps = 0, n_pend = 0, n_hops = 0;  // (wprof: tree_prof diagnostics)
   const uint32_t b = xcd_tile(blockIdx.x, gridDim.x), d = wblk_doc[b];
   const uint32_t W = doc_W[d], Wcap = doc_Wcap[d];
   const uint32_t w0 = wblk_w0[b], w1 = min(w0 + walk_span, W);
@@ -3241,7 +3241,7 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
   __shared__ uint32_t wtot[NT / 64];
   __shared__ uint32_t bad_s, next_j;
   unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = 0;
-  auto stamp = [&](int ph) {  // diagnostic phase times (CW_TREE_PROF)
+  auto stamp = [&](int ph) {  // diagnostic phase times (tree_prof)
     if (tprof) {
       const unsigned long long now = __builtin_amdgcn_s_memtime();
       if (ph >= 0) tacc[ph] += now - tlast;
@@ -3442,7 +3442,7 @@ __global__ __launch_bounds__(NT) void k_tour(const uint32_t *__restrict__ link,
   tour_doc<NT>(link, sval, doc_off, doc_log2k, skey, ts_shift, max_ts, perm, vbits, vcount, status, loc, tprof, doc0 + blockIdx.x, lds_t);
 }
 
-// --- the whole weave of one document in ONE workgroup (CW_FUSED, round 3) -------
+// --- the whole weave of one document in ONE workgroup (option fused, round 3) -------
 // front end, tree and tour of document blockIdx.x back to back: the three
 // phases reuse the same LDS, the handoffs (par, class bitmaps, sval; nsc, fcS;
 // link) go through memory written by this workgroup a moment earlier (its
@@ -3466,7 +3466,7 @@ __global__ __launch_bounds__(NT) void k_weave_doc(
     uint32_t site_mask) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_w[];
   const uint32_t d = blockIdx.x;
-  // (tprof, CW_TREE_PROF: the three phases' clocks per document)
+  // (tprof, tree_prof: the three phases' clocks per document)
   const unsigned long long t0 = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
   // FV (CW_FRONT_U): items in flight per thread in the front end's directory
   // and input-index passes (1: 16, 0: 4 as in k_front); the rank pass loads
@@ -4344,33 +4344,34 @@ struct cw_ctx {
   } tab;
   bool tab_on_device = false;
   bool last_giant = false;
-  // These initialisers are the only statement of a default: cw_ctx_create
-  // overwrites a field whose CW_* variable is set, and nothing else.
+  // These initialisers are the only statement of a default; cw_ctx_set_option
+  // (the OPTIONS table below) is the only writer of the fields it names.
   // launch geometry (round 5: the A/B knobs CW_TB, CW_WALK_THREADS, CW_WALK_SPAN,
   // CW_LOG2K, CW_LOG2CAP and CW_MAX_DIGIT are gone, their measured values stay):
   // one walker per thread (span == threads: a dynamic walker queue per block was slower)
   uint32_t tb = 1024, walk_threads = 512, walk_span = 512, min_log2k = MIN_LOG2K, min_log2cap = 4,
            max_digit = MAX_DIGIT;
-  uint32_t giant_log2cap = 5;      // CW_GIANT_LOG2CAP: walk slot entries of a giant document
-  uint32_t glocal_min = 1u << 20;  // CW_GLOCAL_MIN: a giant tree of this many nodes links siblings
+  uint32_t giant_log2cap = 5;      // giant_log2cap: walk slot entries of a giant document
+  uint32_t glocal_min = 1u << 20;  // glocal_min: a giant tree of this many nodes links siblings
                                    // tile by tile (k_glocal) and sorts only cross-tile children
-  // rank-directory front end (CW_FRONT, CW_FRONT_SLOT bytes per document)
-  uint32_t front = 1, front_slot_groups = 4096, front_min_avg = 1024;
+  // rank-directory front end (front; front_slot: directory bytes per document,
+  // 16-byte groups; front_min_avg: least average document size that takes it)
+  uint32_t front = 1, front_slot = 65536, front_min_avg = 1024;
   uint32_t *pin_small = nullptr;  // pinned 16-byte readback
-  uint32_t tree_prof = 0;          // CW_TREE_PROF: diagnostic phase stamps
-  uint32_t tree_l = 2048;          // CW_TREE_L: k_tree_l (tables in LDS) when the largest document fits: its tile (2048 or 1024; 0 = k_tree)
-  uint32_t gdir = 32;              // CW_GDIR: MiB of global rank directory a giant document may use
-  uint32_t gjoin = 1;              // CW_GJOIN: the giant path joins through a directory of its sorted ids
-  uint32_t map_small = 1;          // CW_MAP_SMALL: one wave per key weave of <= 64 nodes
-  uint32_t pack_sort = 1;          // CW_PACK_SORT: in-LDS sort of packs of small documents
-  uint32_t giant_min = 1u << 16;   // CW_GIANT_MIN: a one-document batch this large uses the giant tree
-  uint32_t tour = 1;               // CW_TOUR: fused LDS tour for documents of < 2^16 nodes
-  uint32_t giant_docs_max = 32;    // CW_GIANT_DOCS: batches of up to this many large documents
+  uint32_t tree_prof = 0;          // tree_prof: diagnostic phase stamps
+  uint32_t tree_l = 2048;          // tree_l: k_tree_l (tables in LDS) when the largest document fits: its tile (2048 or 1024; 0 = k_tree)
+  uint32_t gdir = 32;              // gdir: MiB of global rank directory a giant document may use
+  uint32_t gjoin = 1;              // gjoin: the giant path joins through a directory of its sorted ids
+  uint32_t map_small = 1;          // map_small: one wave per key weave of <= 64 nodes
+  uint32_t pack_sort = 1;          // pack_sort: in-LDS sort of packs of small documents
+  uint32_t giant_min = 1u << 16;   // giant_min: a one-document batch this large uses the giant tree
+  uint32_t tour = 1;               // tour: fused LDS tour for documents of < 2^16 nodes
+  uint32_t giant_docs_max = 32;    // giant_docs: batches of up to this many large documents
                                    // go through the giant path document by document
-  uint32_t front_fused = 1;        // CW_FRONT_FUSED: one-kernel front end (k_front)
-  uint32_t tour_log2k = 3;         // CW_TOUR_LOG2K: nodes per splitter block on that path
-  uint32_t giant_log2k = 4;        // CW_GIANT_LOG2K: least splitter block of a giant document
-  uint32_t fused = 1;              // CW_FUSED: front end + tree + tour in one kernel (k_weave_doc)
+  uint32_t front_fused = 1;        // front_fused: one-kernel front end (k_front)
+  uint32_t tour_log2k = 3;         // tour_log2k: nodes per splitter block on that path
+  uint32_t giant_log2k = 4;        // giant_log2k: least splitter block of a giant document
+  uint32_t fused = 1;              // fused: front end + tree + tour in one kernel (k_weave_doc)
   bool x_hint = true;              // the last list weave may have flagged documents (exact.hip)
   uint32_t n_cu = 256;             // compute units of the device (histogram grid)
   const void *os_lb = nullptr;     // onesweep.hip's look-back words: buffer, size, last epoch
@@ -4379,8 +4380,8 @@ struct cw_ctx {
   const uint32_t *last_dyn = nullptr;  // the last HBM walk's continued-sublist counters
   uint32_t last_dyn_n = 0;             // ... (one per document of that walk)
   uint32_t x_iters = 0;            // synthetic-list weaves of the last exact path (exact.hip)
-  uint32_t xfold = 0;              // CW_XFOLD: documents with an early node take the serial fold
-  uint32_t x_round_cap = 48;       // CW_X_ROUND_CAP: anchor rounds before a small still-moving
+  uint32_t xfold = 0;              // xfold: documents with an early node take the serial fold
+  uint32_t x_round_cap = 48;       // x_round_cap: anchor rounds before a small still-moving
                                    // document takes the serial fold (exact.hip X_ROUND_CAP)
   uint32_t *pin_status = nullptr;  // pinned: a giant document's status, copied after the front end
   hipEvent_t ev_status = nullptr;  // ... and recorded there (exact.hip waits on it, not the stream)
@@ -4394,7 +4395,7 @@ struct cw_ctx {
     uint32_t n = 0;
     bool ok = false;
   } xfront;
-  uint32_t map_fused = 1;          // CW_MAP_FUSED: one-kernel map weave of small collections
+  uint32_t map_fused = 1;          // map_fused: one-kernel map weave of small collections
   struct MapPacks {                // k_map_pack's pack table, cached by collection layout
     std::vector<uint64_t> off;
     std::vector<uint32_t> doc0;
@@ -4581,7 +4582,7 @@ void build_tables(cw_ctx *c, uint64_t D, const uint64_t *off, bool giant) {
     // list fits the device with them (round 5: the rule was n < 2^30, and the
     // 2e9-node walk ran 1.8x slower a node than at 5.4e8 -- the same loads,
     // L2 misses and HBM bytes a node, twice the continuation sublists;
-    // DESIGN 5e).  (CW_GIANT_LOG2CAP: the tests shrink it to send walks
+    // DESIGN 5e).  (giant_log2cap: the tests shrink it to send walks
     // through many continuation sublists)
     // (the knob sets the giant slot size itself, also below min_log2cap)
     // The test is against the device memory free at this call plus the
@@ -4992,6 +4993,8 @@ int weave_tail(cw_ctx *c, uint64_t D, uint32_t N, bool giant, const uint32_t *pa
   uint32_t *slots = nullptr, *dyn_ctr = nullptr, *wcnt = nullptr, *wnext = nullptr,
            *sbase = nullptr, *order = nullptr;
   if (hbm_walk) {
+    c->last_dyn = nullptr;  // (cw_weave_ranked and the like start here: dyn_ctr may move)
+    c->last_dyn_n = 0;
     slots = scratch_t<uint32_t>(c, "slots", t.slots);
     dyn_ctr = scratch_t<uint32_t>(c, "dyn_ctr", D);
     // (one giant document: u64 {count, next} words, see k_walk)
@@ -5325,6 +5328,386 @@ int weave_tail(cw_ctx *c, uint64_t D, uint32_t N, bool giant, const uint32_t *pa
   return 0;
 }
 
+// One call of weave_lists_device: its arguments, and the scratch and tables
+// its front ends share.
+struct ListWeave {
+  cw_ctx *c;
+  const cw_list_batch *bt;
+  const uint64_t *id_key, *cause_key;
+  const uint8_t *kind;
+  cw_list_result *out;
+  uint64_t D;
+  uint32_t N, key_bits;
+  bool giant;       // one giant document (is_giant)
+  bool want_yarns;
+  uint64_t *skA, *skB;  // the id sort's ping-pong pairs (keys, values)
+  uint32_t *svA, *svB;
+  uint32_t *par;        // every front end's output: the cause's rank and the kind, by rank
+  uint8_t *skind;
+  uint32_t *nsc;        // two of the tail's node arrays (the fused kernel writes them)
+  uint64_t *link;
+  uint32_t *tile_start, *tile_doc, *doc_off;  // device tables
+};
+
+// What a front end (steps 1-2: id order and join) hands to the tail.
+struct Front {
+  uint64_t *skey = nullptr;  // the ids in rank order, or nullptr (not written)
+  uint32_t *sval = nullptr;  // the input index of each rank
+  uint32_t *kbm = nullptr;   // special / hide bitmaps per tile (front end -> tree)
+  bool done = false;         // par and skind are written: no other front end runs
+  bool fused_done = false;   // k_weave_doc wove the documents as well: no tail
+  bool yarns_fused = false;  // ... and k_yarn_doc wrote the yarns: no yarn sort
+};
+
+// The phase stamps of a tree_prof run: the sum over the documents of the first
+// `phases` of each document's `stride` clocks (waits for the stream).
+int read_stamps(cw_ctx *c, const unsigned long long *tprof, uint64_t D, int stride, int phases,
+                double *acc) {
+  std::vector<unsigned long long> h((size_t)D * 8);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h.data(), tprof, (size_t)D * 64, hipMemcpyDeviceToHost));
+  for (int ph = 0; ph < phases; ph++) acc[ph] = 0;
+  for (uint64_t dd = 0; dd < D; dd++)
+    for (int ph = 0; ph < phases; ph++) acc[ph] += (double)h[dd * stride + ph];
+  return 0;
+}
+
+// Front end 1, fused per document: documents of < 2^16 nodes whose ids fit a
+// 40 KiB directory.  k_weave_doc (the whole weave in one kernel, then
+// k_yarn_doc) where every phase fits, k_front otherwise.  A document whose ids
+// leave the directory undoes it: f stays empty for the next front end.
+int front_fused(const ListWeave &w, Front *f) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  const cw_list_batch *bt = w.bt;
+  cw_list_result *out = w.out;
+  const uint64_t D = w.D;
+  const uint32_t N = w.N;
+  if (!(c->front && c->front_fused && N >= (uint64_t)c->front_min_avg * D &&
+        t.nmax <= 0xFFFFu && front_lds_bytes(t.nmax, FRONT_FUSED_SG) <= c->lds_max - 1024))
+    return 0;
+  uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
+  uint16_t *rank16 = scratch_t<uint16_t>(c, "fr_rank16", N);
+  f->kbm = scratch_t<uint32_t>(c, "fr_kbm", (size_t)t.T * KBM_WORDS);
+  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+  if (!big || !rank16 || !f->kbm) return fail(c, "out of device memory (front)");
+  HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
+  f->sval = w.svA;
+  // the yarns by k_yarn_doc after the fused kernel (site fields of <= 4
+  // bits, the document's sites and yarn in LDS): no ids in rank order
+  // written, no sort by site afterwards
+  f->yarns_fused = w.want_yarns && bt->site_bits <= 4 && yarn_lds_bytes(t.nmax) + 64 <= c->lds_max;
+  unsigned long long *tprof_f = nullptr;
+  if (c->tree_prof) {
+    tprof_f = scratch_t<unsigned long long>(c, "tprof3", (size_t)D * 8);
+    HIPCHK(c, hipMemsetAsync(tprof_f, 0, (size_t)D * 64, c->stream));
+  }
+  // the whole weave in one kernel when every phase fits: k_tree_l's
+  // 2,048-rank tiles and the fused tour (option fused)
+  const uint32_t fr_lds = front_lds_bytes(t.nmax, FRONT_FUSED_SG);
+  const uint32_t tl_lds = tree_l_lds_bytes(t.nmax) + tree_l_tile_bytes(1024, 2048);
+  const uint32_t to_lds = tour_lds_bytes(t.nmax, t.tour_log2k);
+  const uint32_t wd_lds = std::max(fr_lds, std::max(tl_lds, to_lds));
+  // (the fused kernel needs k_tree_l's 2,048-rank tiles: tree_l = 0 or
+  // 1024 run the separate kernels)
+  f->fused_done = c->fused && t.tour && !w.giant && c->tree_l == 2048 &&
+                  tl_lds + 64 * 4 + 4 <= c->lds_max &&
+                  wd_lds + 1024 <= c->lds_max && to_lds <= TOUR_LDS_MAX;
+  // (k_front writes the ids for the yarn sort)
+  f->yarns_fused = f->yarns_fused && f->fused_done;
+  f->skey = w.want_yarns && !f->yarns_fused ? w.skA : nullptr;
+  if (f->fused_done) {
+    uint32_t *fcS = scratch_t<uint32_t>(c, "fcS", N), *thr = scratch_t<uint32_t>(c, "thr", N);
+    uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", N);
+    if (!fcS || !thr || !loc)
+      return fail(c, "out of device memory (fused weave)");
+    const uint32_t kbits_t = ceil_log2((uint64_t)t.nmax + 1) + 1;
+    // par and (without yarns, which sort by it) sval as u16, no skind
+    uint16_t *par16 = scratch_t<uint16_t>(c, "par16", N);
+    // the site of every input, for k_yarn_doc (one byte a node)
+    uint8_t *site8 = f->yarns_fused ? scratch_t<uint8_t>(c, "site8", N) : nullptr;
+    if (f->yarns_fused && !site8) return fail(c, "out of device memory (fused weave)");
+    const bool wy = w.want_yarns && !f->yarns_fused;  // (u32 sval: the yarn sort's values)
+    uint16_t *sval16 = wy ? nullptr : scratch_t<uint16_t>(c, "sval16", N);
+    if (!par16 || (!wy && !sval16))
+      return fail(c, "out of device memory (fused weave)");
+    // algorithmic bytes: front end (ids twice, causes, kinds, the rank scratch
+    // out and back, par 2, sval 2 or 4, class bitmaps), tree (par 2, kind bits;
+    // fcS clear 4, nsc 4; fcS + nsc back 8, link 4), tour (link 4, sval, the
+    // (sublist, index) records out and back 8, weave_perm 4, bits)
+    const double sv = w.want_yarns ? 4 : 2;
+    Launch L(c, "weave", (double)N * (8 + 8 + 8 + 1 + 2 + 2 + 2 + sv + (f->skey ? 16 : 0) + (site8 ? 1 : 0) + 0.25) +
+                             (double)N * (2 + 0.25 + 4 + 4 + 8 + 4) +
+                             (double)N * (4 + sv + 8 + 4 + 0.125));
+    auto launch = [&](auto kern, auto *sv_ptr) {
+      hipLaunchKernelGGL(kern, dim3((uint32_t)D), dim3(1024), (size_t)wd_lds, c->stream, w.id_key,
+                         w.cause_key, w.kind, w.doc_off, dev_tab(c, "t_tile_first"), FRONT_FUSED_SG, par16,
+                         nullptr, sv_ptr, f->kbm, f->skey, rank16, out->max_ts, bt->ts_shift, out->status,
+                         big, dev_tab(c, "t_doc_log2k"), kbits_t, (t.nmax + 31) / 32, w.nsc, fcS,
+                         (uint32_t *)w.link, thr, out->weave_perm, out->visible_bits,
+                         out->visible_count, loc, tprof_f, site8, bt->site_shift,
+                         (1u << bt->site_bits) - 1u);
+    };
+    if (tprof_f) {  // (the default front-end depth, so the clocks are the product's)
+      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, true, 4, 1>, f->sval);
+      else launch(k_weave_doc<1024, 2048, uint16_t, true, 4, 1>, sval16);
+    } else {
+      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, false, 4, 1>, f->sval);
+      else launch(k_weave_doc<1024, 2048, uint16_t, false, 4, 1>, sval16);
+    }
+  } else {
+    Launch L(c, "front", (double)N * (8 + 8 + 1 + 2 + 4 + 1 + 2 + 4 + (f->skey ? 16 : 0)) + (double)N * 8);
+    hipLaunchKernelGGL(k_front<1024>, dim3((uint32_t)D), dim3(1024),
+                       (size_t)fr_lds, c->stream, w.id_key,
+                       w.cause_key, w.kind, w.doc_off, dev_tab(c, "t_tile_first"), FRONT_FUSED_SG, w.par,
+                       w.skind, f->sval, f->kbm, f->skey, rank16, out->max_ts, bt->ts_shift, out->status, big,
+                       tprof_f);
+  }
+  if (check_launch(c, f->fused_done ? "weave" : "front")) return -1;
+  if (tprof_f) {
+    double a[6];
+    if (read_stamps(c, tprof_f, D, f->fused_done ? 4 : 8, f->fused_done ? 3 : 6, a)) return -1;
+    if (f->fused_done)
+      fprintf(stderr, "weave phases (memtime ticks per doc): front %.0f tree %.0f tour %.0f\n", a[0] / D,
+              a[1] / D, a[2] / D);
+    else
+      fprintf(stderr, "front phases (memtime ticks per doc): dir %.0f rank %.0f write %.0f sval %.0f "
+              "svwrite %.0f\n", a[0] / D, a[1] / D, a[2] / D, a[3] / D, a[4] / D);
+  }
+  HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->pin_small[0] == 0) {
+    f->done = true;
+    c->x_hint = c->pin_small[1] != 0;  // flagged documents, for the exact path
+    if (f->fused_done && f->yarns_fused) {
+      Launch L(c, "yarns", (double)N * (1 + 2 + 2 + 4));
+      hipLaunchKernelGGL(k_yarn_doc<1024>, dim3((uint32_t)D), dim3(1024), (size_t)yarn_lds_bytes(t.nmax),
+                         c->stream, (const uint8_t *)c->bufs["site8"].p, rank16,
+                         (const uint16_t *)c->bufs["sval16"].p, w.doc_off, out->yarn_perm);
+    }
+    if (check_launch(c, "yarns")) return -1;
+  } else {  // a document's ids leave the small directory: the three-kernel front end
+    HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
+    if (f->fused_done) {  // (and the separate tree and tour: the fused kernel stopped early)
+      HIPCHK(c, hipMemsetAsync(out->visible_count, 0, D * 4, c->stream));
+      if (out->visible_bits)
+        HIPCHK(c, hipMemsetAsync(out->visible_bits, 0, ((size_t)N + 31) / 32 * 4, c->stream));
+    }
+    *f = Front{};
+  }
+  return 0;
+}
+
+// Front end 2: one giant document whose ids fit a global rank directory
+// (DESIGN 5e): no id sort, no bucket index, no searching join.
+// (a directory larger than the caches makes k_gd_set's atomics HBM round
+// trips: 6.7e7 nodes over 2^31 keys took 12.8 ms against 8.3 for sort +
+// join, so the directory is taken only while it stays small)
+int front_giant_dir(const ListWeave &w, Front *f) {
+  cw_ctx *c = w.c;
+  const uint32_t N = w.N, key_bits = w.key_bits;
+  if (!(c->gdir && w.giant && key_bits <= GD_MAX_BITS &&
+        (1ull << key_bits) / GD_KEYS * GD_WORDS * 4 <= (uint64_t)c->gdir * (1ull << 20)))
+    return 0;
+  const uint64_t E = ((1ull << key_bits) + GD_KEYS - 1) / GD_KEYS;
+  const uint32_t nb = (uint32_t)((E + 1023) / 1024);
+  uint32_t *dir = scratch_t<uint32_t>(c, "gd_dir", E * GD_WORDS);
+  uint32_t *sums = scratch_t<uint32_t>(c, "gd_sums", nb + 1);
+  unsigned long long *maxid = scratch_t<unsigned long long>(c, "gd_max", 1);
+  if (!(dir && sums && maxid)) return 0;  // (no room for the directory: sort and join)
+  HIPCHK(c, hipMemsetAsync(dir, 0, E * GD_WORDS * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(maxid, 0, 8, c->stream));
+  const dim3 GN((N + 255) / 256);
+  {
+    Launch L(c, "gdir", (double)N * 8 + (double)E * GD_WORDS * 4 * 2);
+    hipLaunchKernelGGL(k_gd_set, GN, dim3(256), 0, c->stream, w.id_key, N, E, dir, maxid,
+                       w.out->status);
+    hipLaunchKernelGGL(k_gd_count, dim3(nb), dim3(1024), 0, c->stream, dir, E, sums);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nb, sums + nb);
+    hipLaunchKernelGGL(k_gd_add, dim3(nb), dim3(1024), 0, c->stream, dir, E, sums);
+  }
+  if (check_launch(c, "gdir")) return -1;
+  f->skey = w.want_yarns ? w.skA : nullptr;
+  f->sval = w.svA;
+  {
+    // (SURVEY 8d's bytes: ids, causes and kinds in, par, kind, sval (and keys)
+    // out -- not the directory lines each lookup touches: those are traffic)
+    Launch L(c, "gplace", (double)N * (8 + 8 + 1 + 4 + 1 + 4 + (f->skey ? 8 : 0)));
+    hipLaunchKernelGGL(k_gd_place, GN, dim3(256), 0, c->stream, w.id_key, w.cause_key, w.kind, N,
+                       reinterpret_cast<const uint4 *>(dir), maxid, w.bt->ts_shift, w.out->max_ts,
+                       w.par, w.skind, f->sval, f->skey, w.out->status);
+  }
+  if (check_launch(c, "gplace")) return -1;
+  f->done = true;
+  return 0;
+}
+
+// Front end 3: a rank directory per document in three kernels (k_fdir, k_frank,
+// k_fplace).  A document whose ids are too sparse for its slot leaves the
+// whole batch to the sort.
+int front_dir3(const ListWeave &w, Front *f) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  cw_list_result *out = w.out;
+  const uint64_t D = w.D;
+  const uint32_t N = w.N;
+  if (!(c->front && N >= (uint64_t)c->front_min_avg * D && t.nmax <= 64 * TILE)) return 0;
+  const dim3 GT(t.T);
+  const uint32_t SG = c->front_slot / 16;
+  uint4 *dir = scratch_t<uint4>(c, "fr_dir", (size_t)D * SG);
+  uint64_t *dkmin = scratch_t<uint64_t>(c, "fr_kmin", D);
+  uint32_t *dgroups = scratch_t<uint32_t>(c, "fr_groups", D);
+  uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
+  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+  if (!dir || !dkmin || !dgroups || !big) return fail(c, "out of device memory (rank directory)");
+  HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
+  {
+    Launch L(c, "fdir", (double)N * 8 + (double)N / 6.0 * 1.0);  // ids once + directory
+    // few documents: one workgroup reads a whole large document, so keep
+    // 16 loads in flight per lane instead of 4
+    auto *fdir = D <= 64 ? k_fdir<1024, 16> : k_fdir<1024, 4>;
+    hipLaunchKernelGGL(fdir, dim3((uint32_t)D), dim3(1024),
+                       (size_t)SG * 16, c->stream, w.id_key, w.doc_off, SG, dir, dkmin, dgroups,
+                       out->max_ts, w.bt->ts_shift, out->status, big);
+  }
+  if (check_launch(c, "fdir")) return -1;
+  HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const uint32_t nbig = c->pin_small[0], gmax = c->pin_small[1];
+  if (nbig) {
+    // some document's ids are too sparse for a slot: general path for the batch
+    HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
+    return 0;
+  }
+  f->skey = w.want_yarns ? w.skA : nullptr;
+  f->sval = w.svA;
+  uint32_t *rec_meta = w.svB, *rec_par = (uint32_t *)w.skB;  // free until the yarn sort
+  uint32_t *woff = scratch_t<uint32_t>(c, "fr_woff", t.Wofftot);
+  f->kbm = scratch_t<uint32_t>(c, "fr_kbm", (size_t)t.T * KBM_WORDS);
+  if (!woff || !f->kbm) return fail(c, "out of device memory (window table)");
+  {
+    Launch L(c, "frank", (double)N * (8 + 8 + 1 + 4 + 4));
+    hipLaunchKernelGGL((k_frank<512>), GT, dim3(512),
+                       std::max<size_t>((size_t)gmax * 16, 2 * TILE * 4),
+                       c->stream, w.id_key, w.cause_key, w.kind, w.tile_start, w.tile_doc,
+                       dev_tab(c, "t_tile_first"), w.doc_off, dev_tab(c, "t_woff_base"), dir,
+                       SG, dkmin, dgroups, rec_meta, rec_par, woff, out->status);
+  }
+  if (check_launch(c, "frank")) return -1;
+  {
+    Launch L(c, "fplace", (double)N * (4 + 4 + 4 + 4 + 1 + (f->skey ? 16 : 0)));
+    hipLaunchKernelGGL((k_fplace<512>), GT, dim3(512), 0, c->stream, rec_meta, rec_par,
+                       woff, dev_tab(c, "t_woff_base"), w.tile_start, w.tile_doc,
+                       dev_tab(c, "t_tile_first"), w.doc_off, w.id_key, f->sval, w.par, w.skind, f->skey,
+                       f->kbm);
+  }
+  if (check_launch(c, "fplace")) return -1;
+  f->done = true;
+  return 0;
+}
+
+// Front end 4, for every batch: the id sort, then the join -- one giant
+// document through a rank directory of its sorted ids (k_gd_build), any other
+// batch through the bucket index (k_join).  f->done stays false: the tail
+// takes ::lamport-ts from the sorted ids.
+int front_sort_join(const ListWeave &w, Front *f) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  cw_list_result *out = w.out;
+  const uint64_t D = w.D;
+  const uint32_t N = w.N, key_bits = w.key_bits;
+  const dim3 B256(256);
+  // 1. id sort (one giant document: carrying every node's cause and kind to
+  // rank order, in the giant tree's four u32 buffers, free until the tree)
+  const bool gd_join = w.giant && c->gjoin && key_bits <= GD_MAX_BITS;
+  OsPayloadBufs plb{};
+  OsPayloadBufs *plp = nullptr;
+  if (gd_join && key_bits <= OS_PL_MAX_BITS) {
+    plb.cause = w.cause_key;
+    plb.kind = w.kind;
+    plb.status = out->status;
+    plb.lo[0] = scratch_t<uint32_t>(c, "g_keyA", N);
+    plb.lo[1] = scratch_t<uint32_t>(c, "g_keyB", N);
+    plb.hi = scratch_t<uint32_t>(c, "g_valA", N);
+    if (!plb.lo[0] || !plb.lo[1] || !plb.hi) return fail(c, "out of device memory (id sort)");
+    plp = &plb;
+  }
+  if (radix_sort<uint64_t>(c, "idsort", w.id_key, nullptr, w.skA, w.svA, w.skB, w.svB, key_bits, 0, N,
+                           &f->skey, &f->sval, nullptr, nullptr, nullptr, plp))
+    return -1;
+  uint64_t *skey = f->skey;
+  uint32_t *sval = f->sval;
+
+  // 2. join
+  // one giant document: a rank directory built from the sorted ids answers
+  // each cause with one line (no bucket index, no search)
+  const uint64_t E = ((1ull << std::min(key_bits, 63u)) + GD_KEYS - 1) / GD_KEYS;
+  uint32_t *gdir = nullptr;
+  if (gd_join) gdir = scratch_t<uint32_t>(c, "gd_dir", E * GD_WORDS);
+  if (!gdir) {
+    uint32_t *bkt = scratch_t<uint32_t>(c, "bkt", t.Btot);
+    if (!bkt) return fail(c, "out of device memory (bucket index)");
+    {
+      Launch L(c, "index", (double)N * 8 + (double)t.Btot * 4);
+      if (D == 1 && N > (1u << 16))  // one large document: a thread per id
+        hipLaunchKernelGGL(k_index_flat, dim3((N + 255) / 256), B256, 0, c->stream, skey, N, bkt,
+                           out->status);
+      else
+        hipLaunchKernelGGL(k_index, dim3((uint32_t)D), B256, 0, c->stream, skey, w.doc_off,
+                           dev_tab(c, "t_bkt_off"), bkt, out->status);
+    }
+    if (check_launch(c, "index")) return -1;
+    {
+      Launch L(c, "join", (double)N * (4 + 8 + 8 + 1 + 4 + 1));
+      hipLaunchKernelGGL(k_join, dim3(t.T), dim3(c->tb), 0, c->stream, skey, sval, w.cause_key, w.kind,
+                         bkt, dev_tab(c, "t_bkt_off"), w.tile_start, w.tile_doc, w.doc_off, w.par,
+                         w.skind, out->status);
+    }
+    if (check_launch(c, "join")) return -1;
+    return 0;
+  }
+  {
+    Launch L(c, "index", (double)N * 8 + (double)N / 15 * 64);
+    hipLaunchKernelGGL(k_gd_build, dim3((N + GDB_KEYS - 1) / GDB_KEYS), B256, 0, c->stream, skey, N,
+                       E, gdir, out->status);
+  }
+  if (check_launch(c, "index")) return -1;
+  if (plp && plb.lo_out) {
+    {
+      // SURVEY 8d's join bytes: the cause (with the kind) read, the parent
+      // rank and kind written -- all in rank order now
+      Launch L(c, "join", (double)N * (8 + 4 + 1));
+      hipLaunchKernelGGL(k_gjoin_r, dim3((N + 256 * GJOIN_ITEMS - 1) / (256 * GJOIN_ITEMS)), B256, 0,
+                         c->stream, skey, plb.lo_out, plb.hi, key_bits, N,
+                         reinterpret_cast<const uint4 *>(gdir), E, w.par, w.skind, out->status);
+    }
+    if (check_launch(c, "join")) return -1;
+    // (the exact path gathers causes by input index: the carried ones go
+    // with the giant tree's buffers)
+    c->xfront = {skey, sval, reinterpret_cast<const uint4 *>(gdir), E, nullptr, N, false};
+    return 0;
+  }
+  // cause and kind packed in one word per input node when the ids leave
+  // 9 bits (the id sort's other key buffer is free by now)
+  uint64_t *ckk = key_bits <= 55 ? (skey == w.skA ? w.skB : w.skA) : nullptr;
+  if (ckk) {
+    Launch L(c, "gpack", (double)N * (8 + 1 + 8));
+    hipLaunchKernelGGL(k_gpack, dim3((N + 255) / 256), B256, 0, c->stream, w.cause_key, w.kind, N, ckk);
+  }
+  {
+    // SURVEY 8d's join bytes (the cause read, the parent rank written) plus
+    // the sorted position's input index and kind: not the directory line a
+    // lookup touches (round 5 counted N x 64 of those as algorithmic)
+    Launch L(c, "join", (double)N * (4 + 8 + 8 + 1 + 4 + 1));
+    hipLaunchKernelGGL(k_gjoin, dim3((N + 256 * GJOIN_ITEMS - 1) / (256 * GJOIN_ITEMS)), B256, 0,
+                       c->stream, skey, sval, w.cause_key, w.kind, N, ckk,
+                       reinterpret_cast<const uint4 *>(gdir), E, w.par, w.skind, out->status);
+  }
+  if (check_launch(c, "join")) return -1;
+  c->xfront = {skey, sval, reinterpret_cast<const uint4 *>(gdir), E, ckk, N, false};
+  return 0;
+}
+
 int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_key,
                        const uint64_t *cause_key, const uint8_t *kind, cw_list_result *out) {
   const uint64_t D = bt->n_docs;
@@ -5332,6 +5715,8 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
   auto &t = c->tab;
   const dim3 B256(256);
 
+  c->last_dyn = nullptr;  // no HBM walk in this call yet (cw_get_counter)
+  c->last_dyn_n = 0;
   HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
   c->xfront = cw_ctx::XFront{};
   // one giant document: k_geff zeroes the count, k_pack_bits writes every word
@@ -5357,378 +5742,72 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 
   uint32_t *tile_start = dev_tab(c, "t_tile_start"), *tile_doc = dev_tab(c, "t_tile_doc");
   uint32_t *doc_off = dev_tab(c, "t_doc_off");
-  const dim3 GT(t.T);
-  const dim3 TB(c->tb);
   if (!grid_ok(t.T, std::max(c->tb, SORT_THREADS)) || !grid_ok(t.Bw, c->walk_threads) ||
       !grid_ok(t.Be, 256) || !grid_ok(D, 1024))
     return fail(c, "batch too large for one dispatch (split the batch)");
+  if (!N) return 0;  // empty documents (no root) are flagged by the host wrapper
 
-  if (N) {
-    uint64_t *skey = nullptr;
-    uint32_t *sval = nullptr;
-    const bool want_yarns = out->yarn_perm && bt->site_bits;
-    // 1-2 (dense ids). id order and join through per-document rank directories
-    bool front_done = false, fused_done = false, yarns_fused = false;
-    uint32_t *kbm = nullptr;  // special / hide bitmaps per tile (front end -> tree)
-    // fused front end: documents of < 2^16 nodes whose ids fit a 40 KiB directory
-    if (c->front && c->front_fused && N >= (uint64_t)c->front_min_avg * D &&
-        t.nmax <= 0xFFFFu && front_lds_bytes(t.nmax, FRONT_FUSED_SG) <= c->lds_max - 1024) {
-      uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
-      uint16_t *rank16 = scratch_t<uint16_t>(c, "fr_rank16", N);
-      kbm = scratch_t<uint32_t>(c, "fr_kbm", (size_t)t.T * KBM_WORDS);
-      if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-      if (!big || !rank16 || !kbm) return fail(c, "out of device memory (front)");
-      HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
-      sval = svA;
-      // the yarns by k_yarn_doc after the fused kernel (site fields of <= 4
-      // bits, the document's sites and yarn in LDS): no ids in rank order
-      // written, no sort by site afterwards
-      yarns_fused = want_yarns && bt->site_bits <= 4 && yarn_lds_bytes(t.nmax) + 64 <= c->lds_max;
-      unsigned long long *tprof_f = nullptr;
-      if (c->tree_prof) {
-        tprof_f = scratch_t<unsigned long long>(c, "tprof3", (size_t)D * 8);
-        HIPCHK(c, hipMemsetAsync(tprof_f, 0, (size_t)D * 64, c->stream));
-      }
-      // the whole weave in one kernel when every phase fits: k_tree_l's
-      // 2,048-rank tiles and the fused tour (CW_FUSED)
-      const uint32_t fr_lds = front_lds_bytes(t.nmax, FRONT_FUSED_SG);
-      const uint32_t tl_lds = tree_l_lds_bytes(t.nmax) + tree_l_tile_bytes(1024, 2048);
-      const uint32_t to_lds = tour_lds_bytes(t.nmax, t.tour_log2k);
-      const uint32_t wd_lds = std::max(fr_lds, std::max(tl_lds, to_lds));
-      // (the fused kernel needs k_tree_l's 2,048-rank tiles: CW_TREE_L = 0 or
-      // 1024 run the separate kernels)
-      fused_done = c->fused && t.tour && !giant1 && c->tree_l == 2048 &&
-                   tl_lds + 64 * 4 + 4 <= c->lds_max &&
-                   wd_lds + 1024 <= c->lds_max && to_lds <= TOUR_LDS_MAX;
-      // (k_front writes the ids for the yarn sort)
-      yarns_fused = yarns_fused && fused_done;
-      skey = want_yarns && !yarns_fused ? skA : nullptr;
-      if (fused_done) {
-        uint32_t *fcS = scratch_t<uint32_t>(c, "fcS", N), *thr = scratch_t<uint32_t>(c, "thr", N);
-        uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", N);
-        if (!fcS || !thr || !loc)
-          return fail(c, "out of device memory (fused weave)");
-        const uint32_t kbits_t = ceil_log2((uint64_t)t.nmax + 1) + 1;
-        // par and (without yarns, which sort by it) sval as u16, no skind
-        uint16_t *par16 = scratch_t<uint16_t>(c, "par16", N);
-        // the site of every input, for k_yarn_doc (one byte a node)
-        uint8_t *site8 = yarns_fused ? scratch_t<uint8_t>(c, "site8", N) : nullptr;
-        if (yarns_fused && !site8) return fail(c, "out of device memory (fused weave)");
-        uint16_t *sval16 = want_yarns && !yarns_fused ? nullptr : scratch_t<uint16_t>(c, "sval16", N);
-        if (!par16 || (!(want_yarns && !yarns_fused) && !sval16))
-          return fail(c, "out of device memory (fused weave)");
-        // algorithmic bytes: front end (ids twice, causes, kinds, the rank scratch
-        // out and back, par 2, sval 2 or 4, class bitmaps), tree (par 2, kind bits;
-        // fcS clear 4, nsc 4; fcS + nsc back 8, link 4), tour (link 4, sval, the
-        // (sublist, index) records out and back 8, weave_perm 4, bits)
-        const double sv = want_yarns ? 4 : 2;
-        Launch L(c, "weave", (double)N * (8 + 8 + 8 + 1 + 2 + 2 + 2 + sv + (skey ? 16 : 0) + (site8 ? 1 : 0) + 0.25) +
-                                 (double)N * (2 + 0.25 + 4 + 4 + 8 + 4) +
-                                 (double)N * (4 + sv + 8 + 4 + 0.125));
-        auto launch = [&](auto kern, auto *sv_ptr) {
-          hipLaunchKernelGGL(kern, dim3((uint32_t)D), dim3(1024), (size_t)wd_lds, c->stream, id_key,
-                             cause_key, kind, doc_off, dev_tab(c, "t_tile_first"), FRONT_FUSED_SG, par16,
-                             nullptr, sv_ptr, kbm, skey, rank16, out->max_ts, bt->ts_shift, out->status,
-                             big, dev_tab(c, "t_doc_log2k"), kbits_t, (t.nmax + 31) / 32, nsc, fcS,
-                             (uint32_t *)link, thr, out->weave_perm, out->visible_bits,
-                             out->visible_count, loc, tprof_f, site8, bt->site_shift,
-                             (1u << bt->site_bits) - 1u);
-        };
-        const bool wy = want_yarns && !yarns_fused;  // (u32 sval: the yarn sort's values)
-        if (tprof_f) {  // (the default front-end depth, so the clocks are the product's)
-          if (wy) launch(k_weave_doc<1024, 2048, uint32_t, true, 4, 1>, sval);
-          else launch(k_weave_doc<1024, 2048, uint16_t, true, 4, 1>, sval16);
-        } else {
-          if (wy) launch(k_weave_doc<1024, 2048, uint32_t, false, 4, 1>, sval);
-          else launch(k_weave_doc<1024, 2048, uint16_t, false, 4, 1>, sval16);
-        }
-      } else {
-        Launch L(c, "front", (double)N * (8 + 8 + 1 + 2 + 4 + 1 + 2 + 4 + (skey ? 16 : 0)) + (double)N * 8);
-        hipLaunchKernelGGL(k_front<1024>, dim3((uint32_t)D), dim3(1024),
-                           (size_t)fr_lds, c->stream, id_key,
-                           cause_key, kind, doc_off, dev_tab(c, "t_tile_first"), FRONT_FUSED_SG, par,
-                           skind, sval, kbm, skey, rank16, out->max_ts, bt->ts_shift, out->status, big,
-                           tprof_f);
-      }
-      if (check_launch(c, fused_done ? "weave" : "front")) return -1;
-      if (tprof_f && fused_done) {
-        std::vector<unsigned long long> h((size_t)D * 8);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(h.data(), tprof_f, (size_t)D * 64, hipMemcpyDeviceToHost));
-        double a[3] = {0};
-        for (uint64_t dd = 0; dd < D; dd++)
-          for (int ph = 0; ph < 3; ph++) a[ph] += (double)h[dd * 4 + ph];
-        fprintf(stderr, "weave phases (memtime ticks per doc): front %.0f tree %.0f tour %.0f\n", a[0] / D,
-                a[1] / D, a[2] / D);
-      } else if (tprof_f) {
-        std::vector<unsigned long long> h((size_t)D * 8);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(h.data(), tprof_f, (size_t)D * 64, hipMemcpyDeviceToHost));
-        double a[6] = {0};
-        for (uint64_t dd = 0; dd < D; dd++)
-          for (int ph = 0; ph < 6; ph++) a[ph] += (double)h[dd * 8 + ph];
-        fprintf(stderr, "front phases (memtime ticks per doc): dir %.0f rank %.0f write %.0f sval %.0f "
-                "svwrite %.0f\n", a[0] / D, a[1] / D, a[2] / D, a[3] / D, a[4] / D);
-      }
-      HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (c->pin_small[0] == 0) {
-        front_done = true;
-        c->x_hint = c->pin_small[1] != 0;  // flagged documents, for the exact path
-        if (fused_done && yarns_fused) {
-          Launch L(c, "yarns", (double)N * (1 + 2 + 2 + 4));
-          hipLaunchKernelGGL(k_yarn_doc<1024>, dim3((uint32_t)D), dim3(1024), (size_t)yarn_lds_bytes(t.nmax),
-                             c->stream, (const uint8_t *)c->bufs["site8"].p, rank16,
-                             (const uint16_t *)c->bufs["sval16"].p, doc_off, out->yarn_perm);
-        }
-        if (check_launch(c, "yarns")) return -1;
-      } else {  // a document's ids leave the small directory: the three-kernel front end
-        HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
-        if (fused_done) {  // (and the separate tree and tour: the fused kernel stopped early)
-          fused_done = false;
-          HIPCHK(c, hipMemsetAsync(out->visible_count, 0, D * 4, c->stream));
-          if (out->visible_bits)
-            HIPCHK(c, hipMemsetAsync(out->visible_bits, 0, ((size_t)N + 31) / 32 * 4, c->stream));
-        }
-        sval = nullptr;
-        skey = nullptr;
-        kbm = nullptr;
-      }
-    }
-    // one giant document whose ids fit a global rank directory:
-    // no id sort, no bucket index, no searching join
-    // (a directory larger than the caches makes k_gd_set's atomics HBM round
-    // trips: 6.7e7 nodes over 2^31 keys took 12.8 ms against 8.3 for sort +
-    // join, so the directory is taken only while it stays small)
-    if (!front_done && c->gdir && is_giant(c, D, bt->doc_offsets) && key_bits <= GD_MAX_BITS &&
-        (1ull << key_bits) / GD_KEYS * GD_WORDS * 4 <= (uint64_t)c->gdir * (1ull << 20)) {
-      const uint64_t E = ((1ull << key_bits) + GD_KEYS - 1) / GD_KEYS;
-      const uint32_t nb = (uint32_t)((E + 1023) / 1024);
-      uint32_t *dir = scratch_t<uint32_t>(c, "gd_dir", E * GD_WORDS);
-      uint32_t *sums = scratch_t<uint32_t>(c, "gd_sums", nb + 1);
-      unsigned long long *maxid = scratch_t<unsigned long long>(c, "gd_max", 1);
-      if (dir && sums && maxid) {
-        HIPCHK(c, hipMemsetAsync(dir, 0, E * GD_WORDS * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(maxid, 0, 8, c->stream));
-        const dim3 GN((N + 255) / 256);
-        {
-          Launch L(c, "gdir", (double)N * 8 + (double)E * GD_WORDS * 4 * 2);
-          hipLaunchKernelGGL(k_gd_set, GN, dim3(256), 0, c->stream, id_key, N, E, dir, maxid,
-                             out->status);
-          hipLaunchKernelGGL(k_gd_count, dim3(nb), dim3(1024), 0, c->stream, dir, E, sums);
-          hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, c->stream, sums, nb, sums + nb);
-          hipLaunchKernelGGL(k_gd_add, dim3(nb), dim3(1024), 0, c->stream, dir, E, sums);
-        }
-        if (check_launch(c, "gdir")) return -1;
-        skey = want_yarns ? skA : nullptr;
-        sval = svA;
-        {
-          // (SURVEY 8d's bytes: ids, causes and kinds in, par, kind, sval (and keys)
-          // out -- not the directory lines each lookup touches: those are traffic)
-          Launch L(c, "gplace", (double)N * (8 + 8 + 1 + 4 + 1 + 4 + (skey ? 8 : 0)));
-          hipLaunchKernelGGL(k_gd_place, GN, dim3(256), 0, c->stream, id_key, cause_key, kind, N,
-                             reinterpret_cast<const uint4 *>(dir), maxid, bt->ts_shift, out->max_ts,
-                             par, skind, sval, skey, out->status);
-        }
-        if (check_launch(c, "gplace")) return -1;
-        front_done = true;
-      }
-    }
-    if (!front_done && c->front && N >= (uint64_t)c->front_min_avg * D && t.nmax <= 64 * TILE) {
-      const uint32_t SG = c->front_slot_groups;
-      uint4 *dir = scratch_t<uint4>(c, "fr_dir", (size_t)D * SG);
-      uint64_t *dkmin = scratch_t<uint64_t>(c, "fr_kmin", D);
-      uint32_t *dgroups = scratch_t<uint32_t>(c, "fr_groups", D);
-      uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
-      if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-      if (!dir || !dkmin || !dgroups || !big) return fail(c, "out of device memory (rank directory)");
-      HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
-      {
-        Launch L(c, "fdir", (double)N * 8 + (double)N / 6.0 * 1.0);  // ids once + directory
-        // few documents: one workgroup reads a whole large document, so keep
-        // 16 loads in flight per lane instead of 4
-        auto *fdir = D <= 64 ? k_fdir<1024, 16> : k_fdir<1024, 4>;
-        hipLaunchKernelGGL(fdir, dim3((uint32_t)D), dim3(1024),
-                           (size_t)SG * 16, c->stream, id_key, doc_off, SG, dir, dkmin, dgroups,
-                           out->max_ts, bt->ts_shift, out->status, big);
-      }
-      if (check_launch(c, "fdir")) return -1;
-      HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const uint32_t nbig = c->pin_small[0], gmax = c->pin_small[1];
-      if (nbig == 0) {
-        skey = want_yarns ? skA : nullptr;
-        sval = svA;
-        uint32_t *rec_meta = svB, *rec_par = (uint32_t *)skB;  // free until the yarn sort
-        uint32_t *woff = scratch_t<uint32_t>(c, "fr_woff", t.Wofftot);
-        kbm = scratch_t<uint32_t>(c, "fr_kbm", (size_t)t.T * KBM_WORDS);
-        if (!woff || !kbm) return fail(c, "out of device memory (window table)");
-        {
-          Launch L(c, "frank", (double)N * (8 + 8 + 1 + 4 + 4));
-          hipLaunchKernelGGL((k_frank<512>), GT, dim3(512),
-                             std::max<size_t>((size_t)gmax * 16, 2 * TILE * 4),
-                             c->stream, id_key, cause_key, kind, tile_start, tile_doc,
-                             dev_tab(c, "t_tile_first"), doc_off, dev_tab(c, "t_woff_base"), dir,
-                             SG, dkmin, dgroups, rec_meta, rec_par, woff, out->status);
-        }
-        if (check_launch(c, "frank")) return -1;
-        {
-          Launch L(c, "fplace", (double)N * (4 + 4 + 4 + 4 + 1 + (skey ? 16 : 0)));
-          hipLaunchKernelGGL((k_fplace<512>), GT, dim3(512), 0, c->stream, rec_meta, rec_par,
-                             woff, dev_tab(c, "t_woff_base"), tile_start, tile_doc,
-                             dev_tab(c, "t_tile_first"), doc_off, id_key, sval, par, skind, skey,
-                             kbm);
-        }
-        if (check_launch(c, "fplace")) return -1;
-        front_done = true;
-      } else {
-        // some document's ids are too sparse for a slot: general path for the batch
-        HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
-      }
-    }
-    if (!front_done) {
-    // 1. id sort (one giant document: carrying every node's cause and kind to
-    // rank order, in the giant tree's four u32 buffers, free until the tree)
-    const bool gd_join = is_giant(c, D, bt->doc_offsets) && c->gjoin && key_bits <= GD_MAX_BITS;
-    OsPayloadBufs plb{};
-    OsPayloadBufs *plp = nullptr;
-    if (gd_join && key_bits <= OS_PL_MAX_BITS) {
-      plb.cause = cause_key;
-      plb.kind = kind;
-      plb.status = out->status;
-      plb.lo[0] = scratch_t<uint32_t>(c, "g_keyA", N);
-      plb.lo[1] = scratch_t<uint32_t>(c, "g_keyB", N);
-      plb.hi = scratch_t<uint32_t>(c, "g_valA", N);
-      if (!plb.lo[0] || !plb.lo[1] || !plb.hi) return fail(c, "out of device memory (id sort)");
-      plp = &plb;
-    }
-    if (radix_sort<uint64_t>(c, "idsort", id_key, nullptr, skA, svA, skB, svB, key_bits, 0, N,
-                             &skey, &sval, nullptr, nullptr, nullptr, plp))
-      return -1;
+  // 1-2. id order and join: the first front end that takes the batch
+  const bool want_yarns = out->yarn_perm && bt->site_bits;
+  const ListWeave w{c, bt, id_key, cause_key, kind, out, D, N, key_bits, giant1, want_yarns,
+                    skA, skB, svA, svB, par, skind, nsc, link, tile_start, tile_doc, doc_off};
+  Front f;
+  if (front_fused(w, &f)) return -1;
+  if (!f.done && front_giant_dir(w, &f)) return -1;
+  if (!f.done && front_dir3(w, &f)) return -1;
+  if (!f.done && front_sort_join(w, &f)) return -1;
 
-    // 2. join
-    // one giant document: a rank directory built from the sorted ids answers
-    // each cause with one line (no bucket index, no search)
-    const uint64_t E = ((1ull << std::min(key_bits, 63u)) + GD_KEYS - 1) / GD_KEYS;
-    uint32_t *gdir = nullptr;
-    if (gd_join) gdir = scratch_t<uint32_t>(c, "gd_dir", E * GD_WORDS);
-    if (gdir) {
-      {
-        Launch L(c, "index", (double)N * 8 + (double)N / 15 * 64);
-        hipLaunchKernelGGL(k_gd_build, dim3((N + GDB_KEYS - 1) / GDB_KEYS), B256, 0, c->stream, skey, N,
-                           E, gdir, out->status);
-      }
-      if (check_launch(c, "index")) return -1;
-      if (plp && plb.lo_out) {
-        {
-          // SURVEY 8d's join bytes: the cause (with the kind) read, the parent
-          // rank and kind written -- all in rank order now
-          Launch L(c, "join", (double)N * (8 + 4 + 1));
-          hipLaunchKernelGGL(k_gjoin_r, dim3((N + 256 * GJOIN_ITEMS - 1) / (256 * GJOIN_ITEMS)), B256, 0,
-                             c->stream, skey, plb.lo_out, plb.hi, key_bits, N,
-                             reinterpret_cast<const uint4 *>(gdir), E, par, skind, out->status);
-        }
-        if (check_launch(c, "join")) return -1;
-        // (the exact path gathers causes by input index: the carried ones go
-        // with the giant tree's buffers)
-        c->xfront = {skey, sval, reinterpret_cast<const uint4 *>(gdir), E, nullptr, N, false};
-      } else {
-      // cause and kind packed in one word per input node when the ids leave
-      // 9 bits (the id sort's other key buffer is free by now)
-      uint64_t *ckk = key_bits <= 55 ? (skey == skA ? skB : skA) : nullptr;
-      if (ckk) {
-        Launch L(c, "gpack", (double)N * (8 + 1 + 8));
-        hipLaunchKernelGGL(k_gpack, dim3((N + 255) / 256), B256, 0, c->stream, cause_key, kind, N, ckk);
-      }
-      {
-        // SURVEY 8d's join bytes (the cause read, the parent rank written) plus
-        // the sorted position's input index and kind: not the directory line a
-        // lookup touches (round 5 counted N x 64 of those as algorithmic)
-        Launch L(c, "join", (double)N * (4 + 8 + 8 + 1 + 4 + 1));
-        hipLaunchKernelGGL(k_gjoin, dim3((N + 256 * GJOIN_ITEMS - 1) / (256 * GJOIN_ITEMS)), B256, 0,
-                           c->stream, skey, sval, cause_key, kind, N, ckk,
-                           reinterpret_cast<const uint4 *>(gdir), E, par, skind, out->status);
-      }
-      if (check_launch(c, "join")) return -1;
-      c->xfront = {skey, sval, reinterpret_cast<const uint4 *>(gdir), E, ckk, N, false};
-      }
-    } else {
-    uint32_t *bkt = scratch_t<uint32_t>(c, "bkt", t.Btot);
-    if (!bkt) return fail(c, "out of device memory (bucket index)");
-    {
-      Launch L(c, "index", (double)N * 8 + (double)t.Btot * 4);
-      if (D == 1 && N > (1u << 16))  // one large document: a thread per id
-        hipLaunchKernelGGL(k_index_flat, dim3((N + 255) / 256), B256, 0, c->stream, skey, N, bkt,
-                           out->status);
-      else
-        hipLaunchKernelGGL(k_index, dim3((uint32_t)D), B256, 0, c->stream, skey, doc_off,
-                           dev_tab(c, "t_bkt_off"), bkt, out->status);
-    }
-    if (check_launch(c, "index")) return -1;
-    {
-      Launch L(c, "join", (double)N * (4 + 8 + 8 + 1 + 4 + 1));
-      hipLaunchKernelGGL(k_join, GT, TB, 0, c->stream, skey, sval, cause_key, kind, bkt,
-                         dev_tab(c, "t_bkt_off"), tile_start, tile_doc, doc_off, par, skind,
-                         out->status);
-    }
-    if (check_launch(c, "join")) return -1;
-    }  // bucket index
-    }  // general front end
-
-    // 3-9. tree, walk, rank, emit, visibility
-    // one giant document: its status (domain bits final now) goes to pinned
-    // memory behind an event, so the exact path's check waits for this point
-    // of the stream only, not for the whole weave (no sync between launches)
-    if (is_giant(c, D, bt->doc_offsets)) {
-      if (!c->pin_status) HIPCHK(c, hipHostMalloc((void **)&c->pin_status, 64, hipHostMallocDefault));
-      if (!c->ev_status) HIPCHK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
-      HIPCHK(c, hipMemcpyAsync(c->pin_status, out->status, 4, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipEventRecord(c->ev_status, c->stream));
-      c->x_pending = true;
-    }
-    // A large list the front end flagged for the exact path (exact.hip, which
-    // rewrites every output of it) skips the fast path's tree, tour and yarns:
-    // one wait for the status copy, worth it above 2^22 nodes (the tail of
-    // 6.7e7 nodes is ~9 ms; config 1's 1e5 nodes keep the call sync-free).
-    bool flagged = false;
-    if (c->x_pending && N >= (1u << 22) && bt->key_bits && bt->key_bits < 64) {
-      HIPCHK(c, hipEventSynchronize(c->ev_status));
-      const uint32_t st = c->pin_status[0];
-      flagged = (st & (CW_STATUS_ROOT | CW_STATUS_ORPHAN | CW_STATUS_NON_LAMPORT)) &&
-                !(st & (CW_STATUS_DUP | CW_STATUS_KEY_RANGE | CW_STATUS_INTERNAL));
-      // the sorted ids and the directory stay intact (no tail): the exact path
-      // joins from them instead of sorting again
-      c->xfront.ok = flagged && c->xfront.skey && c->xfront.n == N;
-    }
-    // without yarns the id-sort buffers are free once the ids are joined
-    const bool spare = !want_yarns;
-    if (!fused_done && !flagged &&
-        weave_tail(c, D, N, is_giant(c, D, bt->doc_offsets), par, skind, sval, kbm,
-                   front_done ? nullptr : skey, bt->ts_shift, out, spare ? skA : nullptr,
-                   spare ? skB : nullptr))
-      return -1;
-
-    // 10. yarns: stable partition of the id order by site rank (unless the
-    // fused kernel wrote them)
-    if (want_yarns && !flagged && !(fused_done && yarns_fused)) {
-      uint64_t *yk;
-      uint32_t *yv;
-      uint64_t *ykA = skey == skA ? skB : skA;
-      uint32_t *yvA = sval == svA ? svB : svA;
-      // (skey, sval) stay intact: ping-pong through the free id buffers + link/loc
-      // (the last pass writes yarn_perm itself, without the keys)
-      if (radix_sort<uint64_t>(c, "yarns", skey, sval, ykA, yvA, link, nsc, bt->site_bits,
-                               bt->site_shift, N, &yk, &yv, nullptr, out->yarn_perm))
-        return -1;
-    }
-    // ids of 64 significant bits: the documents with an id >= 2^63 (KEY_RANGE)
-    if (key_bits >= 64) {
-      hipLaunchKernelGGL(k_key_range, GT, B256, 0, c->stream, id_key, tile_start, tile_doc,
-                         out->status);
-      if (check_launch(c, "key_range")) return -1;
-    }
+  // 3-9. tree, walk, rank, emit, visibility
+  // one giant document: its status (domain bits final now) goes to pinned
+  // memory behind an event, so the exact path's check waits for this point
+  // of the stream only, not for the whole weave (no sync between launches)
+  if (giant1) {
+    if (!c->pin_status) HIPCHK(c, hipHostMalloc((void **)&c->pin_status, 64, hipHostMallocDefault));
+    if (!c->ev_status) HIPCHK(c, hipEventCreateWithFlags(&c->ev_status, hipEventDisableTiming));
+    HIPCHK(c, hipMemcpyAsync(c->pin_status, out->status, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_status, c->stream));
+    c->x_pending = true;
   }
-  // empty documents (no root) are flagged by the host wrapper
+  // A large list the front end flagged for the exact path (exact.hip, which
+  // rewrites every output of it) skips the fast path's tree, tour and yarns:
+  // one wait for the status copy, worth it above 2^22 nodes (the tail of
+  // 6.7e7 nodes is ~9 ms; config 1's 1e5 nodes keep the call sync-free).
+  bool flagged = false;
+  if (c->x_pending && N >= (1u << 22) && bt->key_bits && bt->key_bits < 64) {
+    HIPCHK(c, hipEventSynchronize(c->ev_status));
+    const uint32_t st = c->pin_status[0];
+    flagged = (st & (CW_STATUS_ROOT | CW_STATUS_ORPHAN | CW_STATUS_NON_LAMPORT)) &&
+              !(st & (CW_STATUS_DUP | CW_STATUS_KEY_RANGE | CW_STATUS_INTERNAL));
+    // the sorted ids and the directory stay intact (no tail): the exact path
+    // joins from them instead of sorting again
+    c->xfront.ok = flagged && c->xfront.skey && c->xfront.n == N;
+  }
+  // without yarns the id-sort buffers are free once the ids are joined
+  const bool spare = !want_yarns;
+  if (!f.fused_done && !flagged &&
+      weave_tail(c, D, N, giant1, par, skind, f.sval, f.kbm, f.done ? nullptr : f.skey,
+                 bt->ts_shift, out, spare ? skA : nullptr, spare ? skB : nullptr))
+    return -1;
+
+  // 10. yarns: stable partition of the id order by site rank (unless the
+  // fused kernel wrote them)
+  if (want_yarns && !flagged && !(f.fused_done && f.yarns_fused)) {
+    uint64_t *yk;
+    uint32_t *yv;
+    uint64_t *ykA = f.skey == skA ? skB : skA;
+    uint32_t *yvA = f.sval == svA ? svB : svA;
+    // (skey, sval) stay intact: ping-pong through the free id buffers + link/loc
+    // (the last pass writes yarn_perm itself, without the keys)
+    if (radix_sort<uint64_t>(c, "yarns", f.skey, f.sval, ykA, yvA, link, nsc, bt->site_bits,
+                             bt->site_shift, N, &yk, &yv, nullptr, out->yarn_perm))
+      return -1;
+  }
+  // ids of 64 significant bits: the documents with an id >= 2^63 (KEY_RANGE)
+  if (key_bits >= 64) {
+    hipLaunchKernelGGL(k_key_range, dim3(t.T), B256, 0, c->stream, id_key, tile_start, tile_doc,
+                       out->status);
+    if (check_launch(c, "key_range")) return -1;
+  }
   return 0;
 }
 
@@ -6979,37 +7058,6 @@ int cw_ctx_create(int device, cw_ctx **out) {
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0)
       c->n_cu = (uint32_t)ncu;
   }
-  // a field keeps its initialiser (cw_ctx) unless its variable is set
-  auto knob = [](const char *name, uint32_t &field) {
-    if (const char *v = getenv(name)) field = (uint32_t)strtoul(v, nullptr, 0);
-  };
-  knob("CW_FRONT", c->front);
-  knob("CW_TREE_PROF", c->tree_prof);
-  knob("CW_TREE_L", c->tree_l);
-  knob("CW_GDIR", c->gdir);
-  knob("CW_GJOIN", c->gjoin);
-  knob("CW_GLOCAL_MIN", c->glocal_min);
-  knob("CW_MAP_SMALL", c->map_small);
-  knob("CW_MAP_FUSED", c->map_fused);
-  knob("CW_PACK_SORT", c->pack_sort);
-  knob("CW_GIANT_MIN", c->giant_min);
-  knob("CW_TOUR", c->tour);
-  knob("CW_GIANT_DOCS", c->giant_docs_max);
-  knob("CW_FRONT_FUSED", c->front_fused);
-  knob("CW_TOUR_LOG2K", c->tour_log2k);
-  c->tour_log2k = std::max(MIN_LOG2K, std::min(c->tour_log2k, 12u));
-  knob("CW_GIANT_LOG2K", c->giant_log2k);
-  c->giant_log2k = std::max(MIN_LOG2K, std::min(c->giant_log2k, 12u));
-  knob("CW_GIANT_LOG2CAP", c->giant_log2cap);
-  c->giant_log2cap = std::max(2u, std::min(c->giant_log2cap, 12u));
-  knob("CW_FUSED", c->fused);
-  knob("CW_XFOLD", c->xfold);
-  knob("CW_X_ROUND_CAP", c->x_round_cap);
-  c->x_round_cap = std::max(1u, c->x_round_cap);
-  uint32_t slot_bytes = c->front_slot_groups * 16;
-  knob("CW_FRONT_SLOT", slot_bytes);
-  c->front_slot_groups = std::max(1u, std::min(slot_bytes, 131072u) / 16);
-  knob("CW_FRONT_MIN_AVG", c->front_min_avg);
   *out = c;
   return 0;
 }
@@ -7034,6 +7082,52 @@ void cw_ctx_destroy(cw_ctx *c) {
 }
 
 const char *cw_last_error(const cw_ctx *c) { return c ? c->err.c_str() : "null context"; }
+
+// Every option: its field of cw_ctx (whose initialiser is the default) and
+// the range a value is clamped to.
+static const struct {
+  const char *name;
+  uint32_t cw_ctx::*field;
+  uint32_t lo, hi;
+} OPTIONS[] = {
+    {"front", &cw_ctx::front, 0, UINT32_MAX},
+    {"front_fused", &cw_ctx::front_fused, 0, UINT32_MAX},
+    {"front_slot", &cw_ctx::front_slot, 16, 131072},
+    {"front_min_avg", &cw_ctx::front_min_avg, 0, UINT32_MAX},
+    {"fused", &cw_ctx::fused, 0, UINT32_MAX},
+    {"tour", &cw_ctx::tour, 0, UINT32_MAX},
+    {"tour_log2k", &cw_ctx::tour_log2k, MIN_LOG2K, 12},
+    {"tree_l", &cw_ctx::tree_l, 0, UINT32_MAX},
+    {"tree_prof", &cw_ctx::tree_prof, 0, UINT32_MAX},
+    {"pack_sort", &cw_ctx::pack_sort, 0, UINT32_MAX},
+    {"gdir", &cw_ctx::gdir, 0, UINT32_MAX},
+    {"gjoin", &cw_ctx::gjoin, 0, UINT32_MAX},
+    {"glocal_min", &cw_ctx::glocal_min, 0, UINT32_MAX},
+    {"giant_min", &cw_ctx::giant_min, 0, UINT32_MAX},
+    {"giant_docs", &cw_ctx::giant_docs_max, 0, UINT32_MAX},
+    {"giant_log2k", &cw_ctx::giant_log2k, MIN_LOG2K, 12},
+    {"giant_log2cap", &cw_ctx::giant_log2cap, 2, 12},
+    {"map_small", &cw_ctx::map_small, 0, UINT32_MAX},
+    {"map_fused", &cw_ctx::map_fused, 0, UINT32_MAX},
+    {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
+    {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
+};
+
+int cw_ctx_set_option(cw_ctx *c, const char *name, uint32_t value) {
+  if (!c) return -1;
+  if (!name) return fail(c, "null option name");
+  for (const auto &o : OPTIONS) {
+    if (strcmp(name, o.name) != 0) continue;
+    c->*o.field = std::max(o.lo, std::min(value, o.hi));
+    // what was derived from the options is cached by layout alone: the
+    // document tables (tour, splitter blocks, slot sizes) and the map packs
+    c->tab_on_device = false;
+    c->mpack.ok = false;
+    c->mpack.off.clear();
+    return 0;
+  }
+  return fail(c, "unknown option %s", name);
+}
 
 int cw_ctx_set_stream(cw_ctx *c, void *s) {
   if (!c) return -1;

@@ -70,7 +70,7 @@
 // node).  DESIGN.md 5f.
 //
 // The literal fold on one lane per document (k_xfold, ~1 us a node) is kept
-// as a cross-check behind CW_XFOLD=1.
+// as a cross-check behind the option xfold = 1.
 
 constexpr uint32_t X_NIL = 0xFFFFFFFEu;  // cause is nil (the root's, shared.cljc:22-23)
 constexpr uint32_t X_END = 0xFFFFFFFFu;  // no cause in the document / end of the list
@@ -79,7 +79,7 @@ constexpr uint32_t X_MASK = CW_STATUS_ROOT | CW_STATUS_ORPHAN | CW_STATUS_NON_LA
 // not a ::nodes map of the reference (a repeated id), not a K64 key, or a
 // batch the pipeline found inconsistent (ids wider than the declared key_bits)
 constexpr uint32_t X_SKIP = CW_STATUS_DUP | CW_STATUS_KEY_RANGE | CW_STATUS_INTERNAL;
-constexpr uint32_t XFOLD_MAX = 1u << 22;     // CW_XFOLD: the serial fold's largest document
+constexpr uint32_t XFOLD_MAX = 1u << 22;     // xfold: the serial fold's largest document
 constexpr uint32_t X_NONE = 0xFFFFFFFFu;     // not on the synthetic path
 constexpr uint32_t MT_MAX = 0xFFFFFFFFu;     // min-tree padding ("no node")
 
@@ -803,7 +803,7 @@ __global__ __launch_bounds__(256) void k_xsyn_final(
 
 constexpr uint32_t XB_BIT = 0x80000000u;  // anchor word: BEFORE rank (low bits), else AFTER slot
 constexpr uint32_t X_ROUND_CAP = 48;     // rounds before a small still-moving document is folded
-                                         // (the default of cw_ctx::x_round_cap, CW_X_ROUND_CAP)
+                                         // (the default of cw_ctx::x_round_cap, the option x_round_cap)
 constexpr uint32_t X_CAP_FOLD_MAX = 4096;  // ... serially (k_xfold: ~n^2 steps at worst)
 
 // Positions of a layout-2 weave.  from1: round 0's W is phase 1's weave
@@ -1293,7 +1293,7 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
     std::vector<uint32_t> small[2], big;
     for (uint32_t f = 0; f < F; f++) {
       const uint64_t n = xoff[f + 1] - xoff[f];
-      if (c->xfold && h_early[f] && n <= XFOLD_MAX) {  // CW_XFOLD: the serial fold (cross-check)
+      if (c->xfold && h_early[f] && n <= XFOLD_MAX) {  // xfold: the serial fold (cross-check)
         run[f] = 1;
         any_serial = true;
         continue;
@@ -1578,7 +1578,7 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
     }
     if (check_launch(c, "xsyn_emit")) return -1;
   }
-  if (any_serial) {  // CW_XFOLD: the literal fold, one lane a document
+  if (any_serial) {  // xfold: the literal fold, one lane a document
     uint8_t *d_run = x_upload(c, "x_run", run);
     uint32_t *xnext = scratch_t<uint32_t>(c, "x_next", NX);
     if (!d_run || !xnext) return fail(c, "out of device memory (exact path)");

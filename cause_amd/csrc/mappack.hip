@@ -90,7 +90,7 @@ __global__ __launch_bounds__(NT) void k_map_pack(
   // release fences around it)
   constexpr uint32_t IT = PK / NT;
   unsigned long long tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
-  auto stamp = [&](int ph) {  // diagnostic phase times (CW_TREE_PROF)
+  auto stamp = [&](int ph) {  // diagnostic phase times (tree_prof)
     if (tprof) {
       const unsigned long long now = __builtin_amdgcn_s_memtime();
       if (ph >= 0) tacc[ph] += now - tlast;

@@ -121,6 +121,12 @@ int cw_ctx_set_profiling(cw_ctx *ctx, int on);
  * kernel): a sub-millisecond call is then timed with two events instead of
  * two per launch. */
 int cw_ctx_set_profile_only(cw_ctx *ctx, const char *kernel);
+/* Path and geometry options. Every option has the default the library is
+ * measured with; they exist so tests and measurements can send an input down
+ * a path it would not take by size. Takes effect from the next call on this
+ * context. Values are clamped to the option's range. -1 (cw_last_error) for
+ * an unknown name. The names, defaults and ranges: INTEGRATION.md. */
+int cw_ctx_set_option(cw_ctx *ctx, const char *name, uint32_t value);
 
 typedef struct {
   char name[48];

@@ -1,9 +1,9 @@
 """A/B launch-geometry variants of the weave in ONE process on one workload.
 
-    python scripts/sweep.py '[{}, {"CW_FUSED":"0"}]' [--docs 10000] [--rounds 3]
+    python scripts/sweep.py '[{}, {"fused": 0}]' [--docs 10000] [--rounds 3]
 
-Each variant gets its own context (knobs are read at cw_ctx_create); rounds
-interleave the variants; per-kernel ms come from the library's HIP events.
+Each variant is a dict of options (cw_ctx_set_option) for a
+context of its own; rounds interleave the variants; per-kernel ms come from the library's HIP events.
 """
 import argparse
 import dataclasses
@@ -65,11 +65,7 @@ def main():
     # variants visited twice (A B C ... A B C) so drift shows up
     for sweep in range(2):
         for i, v in enumerate(variants):
-            for k, val in v.items():
-                os.environ[k] = str(val)
-            w = abi.Weaver(0)
-            for k in v:
-                del os.environ[k]
+            w = abi.Weaver(0, options=v)
             w.set_stream(torch.cuda.current_stream(dev).cuda_stream)
             w.weave_lists_device(off, g_id.data_ptr(), g_ca.data_ptr(), g_kd.data_ptr(), lay, ptrs)
             torch.cuda.synchronize()

@@ -1,9 +1,9 @@
 """Time VERDICT r5's exact-path case on the GPU: one 2^18-node config-2-shaped
 document with a 16,384-long reverse chain (rank r caused by rank r + 1), against
 the same document without the chain -- device-memory calls (inputs and outputs
-resident), min of 7 after a warm-up, for each knob set given.
+resident), min of 7 after a warm-up, for each set of options given.
 
-    python scripts/time_reverse_chain.py '[{}, {"CW_XFOLD": "1"}]'
+    python scripts/time_reverse_chain.py '[{}, {"xfold": 1}]'
 
 One JSON line per variant: clean and chain ms, the ratio, the exact path's
 rounds (xins_round launches), all launches and the per-stage ms of one chain
@@ -47,17 +47,7 @@ def main():
          "status": torch.empty(1, dtype=torch.int32, device=dev)}
     ptrs = {k: t.data_ptr() for k, t in o.items()}
     for var in variants:
-        old = {k: os.environ.get(k) for k in var}
-        os.environ.update(var)
-        try:
-            w = abi.Weaver(0)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        with w:
+        with abi.Weaver(0, options=var) as w:
             rec = {"variant": var, "nodes": n, "chain": 16_384}
             for name in ("clean", "chain"):
                 call = lambda: w.weave_lists_device(off, g_id.data_ptr(), g_c[name].data_ptr(),

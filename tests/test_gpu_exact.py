@@ -236,10 +236,8 @@ def test_orphan_documents_one_resolve_no_rounds():
 def test_non_lamport_documents_rounds():
     """Non-Lamport causes (a node caused by a younger node, or by its own id)
     next to orphans and clean documents: phase 2's insertion-tree rounds reach
-    the fold's weave; the same batch through the serial fold (CW_XFOLD=1)
+    the fold's weave; the same batch through the serial fold (xfold = 1)
     agrees."""
-    import os
-
     spec = dataclasses.replace(gen.CONFIG2, nodes_per_doc=3000, seed=32)
     rng = np.random.default_rng(32)
     nl = [1, 0, 3, 10, 0, 40, 2, 100]
@@ -253,14 +251,10 @@ def test_non_lamport_documents_rounds():
         assert 1 <= _stage_launches(w, "xins_round") <= 12
         assert "xfold" not in w.kernel_stats()
     assert all(bool(res.status[d] & abi.STATUS_NON_LAMPORT) == (nl[d] > 0) for d in range(len(nl)))
-    os.environ["CW_XFOLD"] = "1"
-    try:
-        with abi.Weaver(0) as w:
-            w.set_profiling(True)
-            check_batch(w, off, idk, ck, kd, spec.layout())
-            assert "xfold" in w.kernel_stats()
-    finally:
-        del os.environ["CW_XFOLD"]
+    with abi.Weaver(0, options={"xfold": 1}) as w:
+        w.set_profiling(True)
+        check_batch(w, off, idk, ck, kd, spec.layout())
+        assert "xfold" in w.kernel_stats()
 
 
 @pytest.mark.parametrize("orphans", [1, 10, 300])
@@ -348,21 +342,20 @@ def test_chain_families_few_rounds():
     assert res.status[3] == 0 and (res.status[[0, 1, 2, 4, 5, 6, 7]] & abi.STATUS_NON_LAMPORT).all()
 
 
-def test_round_cap_hands_still_moving_documents_to_the_serial_fold(monkeypatch):
+def test_round_cap_hands_still_moving_documents_to_the_serial_fold():
     """a small document still moving after the anchor-round cap
     leaves layout 2 for the serial literal fold (only -> run, any_serial; it
     is emitted with the synthetic lists, then overwritten by k_xfold).  With
-    the cap at one round (CW_X_ROUND_CAP) every chain family takes that
+    the cap at one round (x_round_cap) every chain family takes that
     handoff: k_xfold runs and the batch is bit-exact against the literal fold,
     the clean neighbour included."""
     from tests import exact_model as M
 
-    monkeypatch.setenv("CW_X_ROUND_CAP", "1")
     n = 1500
     docs = [M.chain_doc(f, n, random.Random(k)) for k, f in enumerate(M.CHAIN_FAMILIES)]
     docs.insert(2, M.random_doc(random.Random(9), n))
     off, idk, ck, kd, lay = _rank_docs(docs)
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options={"x_round_cap": 1}) as w:
         w.reset_kernel_stats()
         w.set_profiling(True)
         res = check_batch(w, off, idk, ck, kd, lay, method=oracle.METHOD_LITERAL)

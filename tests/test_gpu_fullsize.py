@@ -24,14 +24,12 @@ def mixed():
     return F.config2_mixed(12, 12)
 
 
-@pytest.mark.parametrize("knobs", [{}, {"CW_FUSED": "0"}, {"CW_TOUR": "0"}, {"CW_FRONT": "0"}],
+@pytest.mark.parametrize("knobs", [{}, {"fused": 0}, {"tour": 0}, {"front": 0}],
                          ids=["default", "separate", "hbm-walk", "radix"])
-def test_config2_full_documents_vs_literal(mixed, knobs, monkeypatch):
+def test_config2_full_documents_vs_literal(mixed, knobs):
     off, idk, ck, kd, dirty, lay = mixed
     assert len(dirty) == 24 and dirty.sum() == 12
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options=knobs) as w:
         res = check_batch(w, off, idk, ck, kd, lay, method=oracle.METHOD_LITERAL)
     assert not res.status.any()
 

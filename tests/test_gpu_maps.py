@@ -29,24 +29,13 @@ NIL = (1 << 64) - 1
 def weaver(request):
     """Every way of weaving key weaves: the one-kernel pack path (k_map_pack,
     collections of <= 2048 nodes), one wave per tiny key weave after the
-    general sorts (k_small_weave, LDS pack sorts; CW_MAP_FUSED=0) and the full
-    list pipeline (CW_MAP_SMALL=0, global radix passes)."""
-    import os
-
+    general sorts (k_small_weave, LDS pack sorts; map_fused = 0) and the full
+    list pipeline (map_small = 0, global radix passes)."""
     # "pipeline" also sorts with the global radix passes instead of the LDS packs
-    knobs = {"fused": {"CW_MAP_FUSED": "1"},
-             "small": {"CW_MAP_FUSED": "0", "CW_MAP_SMALL": "1", "CW_PACK_SORT": "1"},
-             "pipeline": {"CW_MAP_FUSED": "0", "CW_MAP_SMALL": "0", "CW_PACK_SORT": "0"}}[request.param]
-    old = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
-    try:
-        w = abi.Weaver(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    options = {"fused": {"map_fused": 1},
+               "small": {"map_fused": 0, "map_small": 1, "pack_sort": 1},
+               "pipeline": {"map_fused": 0, "map_small": 0, "pack_sort": 0}}[request.param]
+    w = abi.Weaver(0, options=options)
     w.fused = request.param == "fused"
     yield w
     w.close()

@@ -19,35 +19,24 @@ from tests import refgen as G
 pytestmark = pytest.mark.gpu
 
 
-# Front ends: "front" = rank directories for every document (CW_FRONT_MIN_AVG=0
-# also sends tiny documents through it; the whole weave of a document in one
-# kernel, k_weave_doc, where it applies), "separate" = k_front, k_tree_l and
-# k_tour as three kernels, "front3" = the three-kernel directory front end,
-# "radix" = segmented radix sort + join.
-FRONTS = {"front": {"CW_FRONT": "1", "CW_FRONT_MIN_AVG": "0"},
-          "separate": {"CW_FRONT": "1", "CW_FRONT_MIN_AVG": "0", "CW_FUSED": "0"},
-          "front3": {"CW_FRONT": "1", "CW_FRONT_MIN_AVG": "0", "CW_FRONT_FUSED": "0"},
-          "radix": {"CW_FRONT": "0"},
-          "radix-global": {"CW_FRONT": "0", "CW_PACK_SORT": "0"},  # no LDS pack sorts
-          "hbm-walk": {"CW_TOUR": "0"},  # walk + rank + emit instead of the LDS tour
-          "hbm-tree": {"CW_TREE_L": "0"}}  # k_tree, tables in HBM
+# Front ends (options of the context, cw_ctx_set_option): "front" = rank
+# directories for every document (front_min_avg = 0 also sends tiny documents
+# through it; the whole weave of a document in one kernel, k_weave_doc, where
+# it applies), "separate" = k_front, k_tree_l and k_tour as three kernels,
+# "front3" = the three-kernel directory front end, "radix" = segmented radix
+# sort + join.
+FRONTS = {"front": {"front": 1, "front_min_avg": 0},
+          "separate": {"front": 1, "front_min_avg": 0, "fused": 0},
+          "front3": {"front": 1, "front_min_avg": 0, "front_fused": 0},
+          "radix": {"front": 0},
+          "radix-global": {"front": 0, "pack_sort": 0},  # no LDS pack sorts
+          "hbm-walk": {"tour": 0},  # walk + rank + emit instead of the LDS tour
+          "hbm-tree": {"tree_l": 0}}  # k_tree, tables in HBM
 
 
 @pytest.fixture(scope="module", params=sorted(FRONTS))
 def weaver(request):
-    import os
-
-    old = {k: os.environ.get(k) for k in FRONTS[request.param]}
-    os.environ.update(FRONTS[request.param])
-    try:
-        w = abi.Weaver(0)  # knobs are read when the context is created
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    with w:
+    with abi.Weaver(0, options=FRONTS[request.param]) as w:
         yield w
 
 
@@ -302,15 +291,19 @@ def test_duplicate_ids_beside_clean_documents(weaver):
         assert np.array_equal(gvis[b:e], vis[b:e])
 
 
-# walk / slot geometry only matters on the HBM walk path (CW_TOUR=0); the
-# fused LDS tour takes its own splitter density (CW_TOUR_LOG2K)
-_W = {"CW_TOUR": "0"}
-KNOBS = [{}, dict(_W),
-         {"CW_TOUR_LOG2K": "3"}, {"CW_TOUR_LOG2K": "4"}, {"CW_TOUR_LOG2K": "7"},
-         {"CW_FRONT": "0"}, {"CW_FRONT_SLOT": "4096"},
+# walk / slot geometry only matters on the HBM walk path (tour = 0); the
+# fused LDS tour takes its own splitter density (tour_log2k)
+KNOBS = [{}, {"tour": 0},
+         {"tour_log2k": 3}, {"tour_log2k": 4}, {"tour_log2k": 7},
+         {"front": 0}, {"front_slot": 4096},
          # the tree: k_tree (tables in HBM, the fallback for documents too large
          # for k_tree_l's LDS), k_tree_l with 1,024-rank tiles, the separate kernels
-         {"CW_TREE_L": "0"}, {"CW_TREE_L": "1024"}, {"CW_FUSED": "0"}]
+         {"tree_l": 0}, {"tree_l": 1024}, {"fused": 0}]
+
+
+def _knob_id(k):
+    # (upper case with the CW_ prefix: the ids earlier test records carry)
+    return ",".join(f"CW_{a.upper()}={b}" for a, b in k.items()) or "default"
 
 
 @pytest.mark.parametrize("n", [59_204, 60_000, 65_534, 65_535])
@@ -328,29 +321,25 @@ def test_tour_document_size_limits(n):
         check_batch(w, off, idk, ck, kd, spec.layout(), method=oracle.METHOD_EFF, yarns=False)
 
 
-@pytest.mark.parametrize("knobs", KNOBS, ids=lambda k: ",".join(f"{a}={b}" for a, b in k.items()) or "default")
-def test_config2_documents_any_geometry(knobs, monkeypatch):
+@pytest.mark.parametrize("knobs", KNOBS, ids=_knob_id)
+def test_config2_documents_any_geometry(knobs):
     """Full-size config-2 documents (50,001 nodes) under every launch geometry
     knob: the output must not depend on splitter density, slot size, digit
     width or walker grouping."""
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
     spec = gen.CONFIG2
     off, idk, ck, kd = gen.generate(spec, 0, 24)
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options=knobs) as w:
         check_batch(w, off, idk, ck, kd, spec.layout(), method=oracle.METHOD_EFF, yarns=False)
 
 
-@pytest.mark.parametrize("knobs", [{}, {"CW_FUSED": "0"}, {"CW_TOUR": "0"}],
+@pytest.mark.parametrize("knobs", [{}, {"fused": 0}, {"tour": 0}],
                          ids=["default", "separate", "hbm-walk"])
-def test_full_bench_batch_vs_oracle(knobs, monkeypatch):
+def test_full_bench_batch_vs_oracle(knobs):
     """The whole bench workload (10,000 config-2 documents, 5e8 nodes) against
     the oracle, every document, plus permutation validity."""
-    for k, v in knobs.items():
-        monkeypatch.setenv(k, v)
     spec = gen.CONFIG2
     off, idk, ck, kd = gen.generate(spec, 0, 10_000, nthreads=32)
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options=knobs) as w:
         res = w.weave_lists(off, idk, ck, kd, spec.layout(), yarns=False)
     assert not res.status.any(), np.nonzero(res.status)[0][:10]
     perm, vis, st = oracle.batch_lists(off, idk, ck, kd, method=oracle.METHOD_EFF, nthreads=32)
@@ -375,27 +364,12 @@ def test_full_bench_batch_vs_oracle(knobs, monkeypatch):
 # ------------------------------------------------- one giant document (config 5)
 # Giant-path front ends: the directory over the whole key range
 # (k_gd_place, small key ranges: the default here), the sorted-id directory
-# join (CW_GDIR=0: k_gd_build / k_gpack / k_gjoin, config 5's default) and
-# the bucket index + searching join (CW_GJOIN=0).
-GIANT_FRONTS = {"gdplace": {}, "gjoin": {"CW_GDIR": "0"},
-                "bucket": {"CW_GDIR": "0", "CW_GJOIN": "0"},
+# join (gdir = 0: k_gd_build / k_gpack / k_gjoin, config 5's default) and
+# the bucket index + searching join (gjoin = 0).
+GIANT_FRONTS = {"gdplace": {}, "gjoin": {"gdir": 0},
+                "bucket": {"gdir": 0, "gjoin": 0},
                 # the tile-local sibling links (k_glocal) at every size
-                "glocal": {"CW_GDIR": "0", "CW_GLOCAL_MIN": "0"}}
-
-
-def _weaver_with(env):
-    import os
-
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return abi.Weaver(0)  # knobs are read when the context is created
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+                "glocal": {"gdir": 0, "glocal_min": 0}}
 
 
 @pytest.fixture(scope="module", params=sorted(GIANT_FRONTS))
@@ -403,7 +377,7 @@ def giant_weaver(request):
     """A context that sends every one-document batch through the giant-document
     tree (k_geff / radix sort / k_gsib / k_gthr + the walk's thread chase),
     under each giant front end."""
-    with _weaver_with(dict(GIANT_FRONTS[request.param], CW_GIANT_MIN="0")) as w:
+    with abi.Weaver(0, options=dict(GIANT_FRONTS[request.param], giant_min=0)) as w:
         yield w
 
 
@@ -457,7 +431,7 @@ def test_id_sort_carried_cause_key_widths(target_bits):
     ck[some[20:39]] = idk.max() + np.uint64(1 << shift)      # past the largest id
     ck[some[39]] = np.uint64(pack.NIL)
     assert lay.key_bits == max(lay0.key_bits, target_bits)
-    with _weaver_with({"CW_GDIR": "0", "CW_GIANT_MIN": "0"}) as w:
+    with abi.Weaver(0, options={"gdir": 0, "giant_min": 0}) as w:
         res = check_batch(w, off, idk, ck, kd, lay, method=oracle.METHOD_GENERAL, yarns=False)
     assert res.status[0] & abi.STATUS_ORPHAN
 
@@ -469,7 +443,7 @@ def test_giant_join_misdeclared_key_bits():
     spec = dataclasses.replace(gen.CONFIG2, nodes_per_doc=100_000, seed=41)
     off, idk, ck, kd = gen.generate(spec, 0, 1)
     lay = spec.layout()
-    with _weaver_with({"CW_GDIR": "0", "CW_GIANT_MIN": "0"}) as w:
+    with abi.Weaver(0, options={"gdir": 0, "giant_min": 0}) as w:
         res = w.weave_lists(off, idk, ck, kd, lay, key_bits=max(1, lay.key_bits - 6))
         assert res.status[0] & abi.STATUS_INTERNAL
         again = w.weave_lists(off, idk, ck, kd, lay)  # the context still works
@@ -493,13 +467,11 @@ def test_giant_path_shapes(giant_weaver):
 
 
 @pytest.mark.parametrize("log2k", ["3", "5"])
-def test_giant_path_splitter_blocks(log2k, monkeypatch):
+def test_giant_path_splitter_blocks(log2k):
     """The giant path under other splitter blocks than its default 16 nodes
-    (CW_GIANT_LOG2K, lists of >= 2^22 nodes): 8 (the round-2 geometry) and 32."""
-    monkeypatch.setenv("CW_GIANT_MIN", "0")
-    monkeypatch.setenv("CW_GIANT_LOG2K", log2k)
+    (giant_log2k, lists of >= 2^22 nodes): 8 (the round-2 geometry) and 32."""
     rng = random.Random(7)
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options={"giant_min": 0, "giant_log2k": int(log2k)}) as w:
         for steps, tx in ((2000, 0.0), (1500, 0.3)):
             d = G.stress_history(rng, steps, tx_chain=tx)
             rng.shuffle(d)
@@ -514,16 +486,14 @@ def test_giant_path_splitter_blocks(log2k, monkeypatch):
         check_batch(w, off, idk, ck, kd, spec.layout(), method=oracle.METHOD_EFF, yarns=False)
 
 
-def test_giant_path_many_continuation_sublists(monkeypatch):
-    """4-entry walk slots (CW_GIANT_LOG2CAP = 2, which sets the giant slot
+def test_giant_path_many_continuation_sublists():
+    """4-entry walk slots (giant_log2cap = 2, which sets the giant slot
     size itself, below the library's 16-entry minimum): every walk goes on
     through several continuation sublists, so the first ranking level's
     walkers pass more sublists than their 32-entry slots hold and the rest
     take the overflow path (pos + the overflow list).  The walk's
     continued-sublist counter proves the overflows happened."""
-    monkeypatch.setenv("CW_GIANT_MIN", "0")
-    monkeypatch.setenv("CW_GIANT_LOG2CAP", "2")
-    with abi.Weaver(0) as w:
+    with abi.Weaver(0, options={"giant_min": 0, "giant_log2cap": 2}) as w:
         spec = dataclasses.replace(gen.CONFIG2, nodes_per_doc=(1 << 22) + 1000)
         off, idk, ck, kd = gen.generate(spec, 0, 1)
         check_batch(w, off, idk, ck, kd, spec.layout(), method=oracle.METHOD_EFF, yarns=False)
@@ -533,8 +503,7 @@ def test_giant_path_many_continuation_sublists(monkeypatch):
         off, idk, ck, kd = gen.generate(gen.CONFIG1, 0, 1)
         check_batch(w, off, idk, ck, kd, gen.CONFIG1.layout(), method=oracle.METHOD_LINKED)
         assert w.counter("continued_sublists") > 0
-    monkeypatch.setenv("CW_GIANT_LOG2CAP", "5")
-    with abi.Weaver(0) as w:  # the default 32-entry slots overflow far less often
+    with abi.Weaver(0, options={"giant_min": 0, "giant_log2cap": 5}) as w:  # the default 32-entry slots overflow far less often
         spec = dataclasses.replace(gen.CONFIG2, nodes_per_doc=(1 << 22) + 1000)
         off, idk, ck, kd = gen.generate(spec, 0, 1)
         w.weave_lists(off, idk, ck, kd, spec.layout())
