@@ -3211,7 +3211,8 @@ __global__ __launch_bounds__(256) void k_emit(
 //          next sublist from an LDS counter as soon as one ends (a wave never
 //          waits for its longest walk); each node's (sublist, index) goes to
 //          HBM scratch with fire-and-forget stores;
-//   jump   suffix sums over the sublists by pointer jumping -> sublist bases;
+//   jump   suffix sums over the sublists by pointer jumping -> sublist bases
+//          (asynchronous: no barrier between the hops);
 //   place  coalesced over nodes: position = base + index, sval (u16) into an
 //          LDS weave where the successors were, render bits by position;
 //   write  weave_perm and render bytes, coalesced.
@@ -3335,40 +3336,82 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
   if (tid == 0) next_j = NT;
   stamp(1);
   // suffix sums along the sublist list by pointer jumping: sub[j] & 0xFFFF = nodes from
-  // sublist j to the end of the tour (<= n < 2^16)
-  for (uint32_t round = 0; (1u << round) < 2 * S; round++) {
-    uint32_t na[SPT], nn[SPT];
+  // sublist j to the end of the tour (<= n < 2^16).  No barriers: a thread
+  // owns the entries j = tid + k NT and hops each until its next is TOUR_END,
+  // sub[j] = (acc_j + acc_q, next_q) for q = next_j.  Every word always holds
+  // a true pair (the nodes from j's start to next_j's start; one 32-bit access
+  // reads or writes both), so a stale sub[q] is still a true pair, a hop
+  // advances by at least one sublist whatever the other waves do, and no lane
+  // waits for another.  Only its owner writes an entry, which it keeps in
+  // registers.  A round hops every live entry (the reads in flight together),
+  // then each once more before it is stored (two reads a store: 20.3k -> 16.8k
+  // clocks a document; three and four lost).  A corrupt link table can close
+  // the sublist list into a cycle: S rounds at the most, then INTERNAL.
+  {
+    auto ld = [&](uint32_t j) {
+      return __hip_atomic_load(&sub[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    auto rank = [&](auto E_) {
+      constexpr uint32_t E = decltype(E_)::value;  // entries a thread: dead slots cost nothing
+      uint32_t a[E], q[E], sq[E];
 #pragma unroll
-    for (uint32_t k = 0; k < SPT; k++) {
-      const uint32_t j = tid + k * NT;
-      if (j < S) {
-        const uint32_t sj = sub[j], q = sj >> 16;
-        const uint32_t sq = q < S ? sub[q] : TOUR_END << 16;
-        na[k] = (sj & 0xFFFFu) + (sq & 0xFFFFu);
-        nn[k] = sq >> 16;
+      for (uint32_t k = 0; k < E; k++) {
+        const uint32_t j = tid + k * NT;
+        const uint32_t sj = j < S ? ld(j) : TOUR_END << 16;
+        a[k] = sj & 0xFFFFu;
+        q[k] = sj >> 16;
       }
-    }
-    __syncthreads();
+      for (uint32_t rounds = 0;; rounds++) {
+        bool more = false;
 #pragma unroll
-    for (uint32_t k = 0; k < SPT; k++) {
-      const uint32_t j = tid + k * NT;
-      if (j < S) {
-        sub[j] = min(na[k], 0xFFFFu) | nn[k] << 16;
+        for (uint32_t k = 0; k < E; k++)
+          if (q[k] < S) sq[k] = ld(q[k]);
+#pragma unroll
+        for (uint32_t k = 0; k < E; k++)
+          if (q[k] < S) {  // (so j < S: a dead slot's next is TOUR_END)
+            a[k] = min(a[k] + (sq[k] & 0xFFFFu), 0xFFFFu);
+            q[k] = sq[k] >> 16;
+            if (q[k] < S) {
+              const uint32_t s2 = ld(q[k]);
+              a[k] = min(a[k] + (s2 & 0xFFFFu), 0xFFFFu);
+              q[k] = s2 >> 16;
+            }
+            __hip_atomic_store(&sub[tid + k * NT], a[k] | q[k] << 16, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_WORKGROUP);
+            more |= q[k] < S;
+          }
+        if (!more) break;
+        if (rounds >= S) {
+          bad = true;
+          break;
+        }
       }
+    };
+    switch ((S + NT - 1) / NT) {  // <= SPT: the host sizes the splitter blocks so
+      case 1: rank(std::integral_constant<uint32_t, 1>()); break;
+      case 2: rank(std::integral_constant<uint32_t, 2>()); break;
+      case 3: rank(std::integral_constant<uint32_t, 3>()); break;
+      case 4: rank(std::integral_constant<uint32_t, 4>()); break;
+      case 5: rank(std::integral_constant<uint32_t, 5>()); break;
+      case 6: rank(std::integral_constant<uint32_t, 6>()); break;
+      case 7: rank(std::integral_constant<uint32_t, 7>()); break;
+      case 8: rank(std::integral_constant<uint32_t, 8>()); break;
+      default: bad = true; break;
     }
-    __syncthreads();
+    static_assert(SPT == 8, "one case per entry count");
   }
   stamp(2);
-  if (tid == 0 && (sub[0] & 0xFFFFu) != n) bad_s = 1;  // the root's sublist starts the tour
   // place: coalesced over nodes, position = sublist base + index; the weave
   // (sval as u16) and its render bits are assembled in LDS where the
   // successors and splitter bits were, then written out coalesced.  (The
   // scratch stores above are read by other waves of this workgroup: one CU,
-  // one L1, lines not cached before; the barriers order them.)
+  // one L1, lines not cached before; the barriers order them.)  The barrier
+  // below is the one that ends the ranking.
   uint16_t *out = succ;
   uint32_t *pvis = sbm;
   for (uint32_t w = tid; w < nw; w += NT) pvis[w] = 0;
   __syncthreads();
+  if (tid == 0 && (sub[0] & 0xFFFFu) != n) bad_s = 1;  // the root's sublist starts the tour
   for (uint32_t r0 = tid; r0 < n; r0 += NT * LU) {
     uint32_t lc[LU], x[LU];
 #pragma unroll
