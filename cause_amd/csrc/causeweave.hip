@@ -1355,7 +1355,8 @@ __host__ __device__ inline uint32_t front_lds_bytes(uint32_t nmax, uint32_t sg) 
 // the width of par / sval (u16 inside k_weave_doc: n < 2^16); skind may be
 // null (the tree reads the class bitmaps).
 // U1 / U2 / U3: items a thread keeps in flight in the directory, rank and
-// input-index passes (the fused kernel's front end is latency-bound: CW_FRONT_U)
+// input-index passes (k_front: 4 / 4 / 4; the fused kernel's front end is
+// latency-bound and takes 16 / 6 / 16, see k_weave_doc)
 template <int NT, typename PT = uint32_t, typename VT = uint32_t, uint32_t U1 = 4, uint32_t U2 = 4,
           uint32_t U3 = 4>
 __device__ __forceinline__ bool front_doc(
@@ -1949,12 +1950,13 @@ __host__ __device__ inline uint32_t tree_l_lds_bytes(uint32_t nmax) {
   return ((nmax + 31) / 32) * 8 + ((nmax + 1) / 2) * 4;  // two bitmaps + u16 table
 }
 
-// MODE 4 (the one built; round 3's A/B variants 0-3 lost and are gone): a
-// group whose parent lies in the tile (69% of config-2 nodes) keeps its list
-// head in a direct table indexed by (class, parent - tile start): one exchange
-// instead of a claiming CAS + exchange; other groups go through the hash
-// one document d (the whole workgroup); lds: the dynamic LDS (16-byte aligned)
-template <int NT, int TILE_T, bool PROF, int MODE, typename PT = uint32_t>
+// One document d (the whole workgroup); lds: the dynamic LDS (16-byte aligned).
+// A tile's sibling groups are member lists in LDS.  A group whose parent lies
+// in the tile (69% of config-2 nodes) keeps its list head in a direct table
+// indexed by (class, parent - tile start): one exchange, no claiming CAS.  The
+// other groups claim a slot of a hash by group key, then exchange on its head.
+// (What the direct heads were measured against: DESIGN §5.)
+template <int NT, int TILE_T, bool PROF, typename PT = uint32_t>
 __device__ __forceinline__ void tree_l_doc(
     const PT *__restrict__ par, const uint8_t *__restrict__ skind,
     const uint32_t *__restrict__ doc_off, const uint32_t *__restrict__ doc_log2k, uint32_t kbits,
@@ -1975,18 +1977,17 @@ __device__ __forceinline__ void tree_l_doc(
   stamp(-1);
   // one tile's group-key hash: hk[slot] = group key (0 = empty), hh[slot] =
   // the head of the slot's member list (a tile index); nxt: next member,
-  // TL_END ends.  The fallback sort's tkey/trank/tns and sweep 2's T live in
-  // the same buffer.
-  static_assert(MODE == 4, "k_tree_l is built with direct list heads only");
-  constexpr bool DH = true;
-  constexpr uint32_t HS = DH ? TILE_T : 2 * TILE_T, GMAX = 16, HB = TILE_T <= 2048 ? 11 : 12;
+  // TL_END ends.  The direct heads follow the hash: hbuf[2 HS + class * TILE_T
+  // + (parent - tile start)].  The fallback sort's tkey/trank/tns and sweep 2's
+  // T live in the same buffer.
+  constexpr uint32_t HS = TILE_T, GMAX = 16, HB = TILE_T <= 2048 ? 11 : 12;
   static_assert(TILE_T <= (1u << HB) && 17 + HB <= 32, "slot word layout");
-  static_assert(2 * HS + (DH ? 2 * TILE_T : 0) == 4 * TILE_T, "hash (+ direct heads) = 4 TILE_T words");
-  uint32_t *const hbuf = lds;  // 4 TILE_T words: hash keys, hash heads (, direct heads)
+  static_assert(2 * HS + 2 * TILE_T == 4 * TILE_T, "hash + direct heads = 4 TILE_T words");
+  uint32_t *const hbuf = lds;  // 4 TILE_T words: hash keys, hash heads, direct heads
   uint32_t(*const wcnt)[SUB_BINS] = reinterpret_cast<uint32_t(*)[SUB_BINS]>(lds + 4 * TILE_T);
   uint16_t *const nxt = reinterpret_cast<uint16_t *>(lds + 4 * TILE_T + (NT / 64) * SUB_BINS);
   uint32_t *const bm = lds + tree_l_tile_bytes(NT, TILE_T) / 4;
-  uint32_t *const hw = hbuf, *const hk = hbuf, *const hh = hbuf + HS;
+  uint32_t *const hk = hbuf, *const hh = hbuf + HS;
   uint32_t *const tkey = hbuf, *const trank = hbuf + TILE_T, *const tns = hbuf + 2 * TILE_T;
   uint32_t *const ptab = tns;
   __shared__ uint32_t run[64];
@@ -2044,11 +2045,10 @@ __device__ __forceinline__ void tree_l_doc(
   // sorted by group key instead, as in k_tree.
   auto clear_hash = [&]() {
     for (uint32_t i = tid; i < HS; i += NT) {
-      hw[i] = 0;
+      hk[i] = 0;
       hh[i] = TL_END;
     }
-    if (DH)
-      for (uint32_t i = tid; i < 2 * TILE_T; i += NT) hbuf[2 * HS + i] = TL_END;
+    for (uint32_t i = tid; i < 2 * TILE_T; i += NT) hbuf[2 * HS + i] = TL_END;
   };
   clear_hash();
   if (tid == 0) n_osp = 0;
@@ -2109,7 +2109,7 @@ __device__ __forceinline__ void tree_l_doc(
       if (j < len && kk) {
         uint32_t h = (kk * 0x9E3779B1u) >> (32 - __builtin_ctz(HS));
         const uint32_t e = (kk >> 1) - 1;
-        if (DH && e >= r0) {  // slot = the head's word in hbuf
+        if (e >= r0) {  // slot = the head's word in hbuf
           const uint32_t s = 2 * HS + (kk & 1) * TILE_T + (e - r0);
           nxt[j] = (uint16_t)atomicExch(&hbuf[s], j);
           slot[k] = s;
@@ -2121,7 +2121,7 @@ __device__ __forceinline__ void tree_l_doc(
           h = (h + 1) & (HS - 1);
         }
         nxt[j] = (uint16_t)atomicExch(&hh[h], j);
-        slot[k] = DH ? HS + h : h;
+        slot[k] = HS + h;
       }
     }
     stamp(11);
@@ -2133,8 +2133,7 @@ __device__ __forceinline__ void tree_l_doc(
 #pragma unroll
     for (uint32_t k = 0; k < IT; k++) {
       const uint32_t j = wb_elem<IT>(k);
-      uint32_t x = !(j < len && key[k]) ? TL_END
-                   : DH ? hbuf[slot[k]] : hh[slot[k]];
+      uint32_t x = !(j < len && key[k]) ? TL_END : hbuf[slot[k]];
       uint32_t p1 = 0, steps = 0;
       bool ls = true;
 #pragma unroll 1
@@ -2224,12 +2223,9 @@ __device__ __forceinline__ void tree_l_doc(
           if (kk & 1) tab[e] = (uint16_t)r;
           else lane_at(fcSD, e) = r;
         }
-        if (kk && DH) {
+        if (kk) {
           if (slot[k] < 2 * HS) hk[slot[k] - HS] = 0;
           hbuf[slot[k]] = TL_END;
-        } else if (kk) {
-          hw[slot[k]] = 0;
-          hh[slot[k]] = TL_END;
         }
       }
       __syncthreads();
@@ -2351,7 +2347,7 @@ __device__ __forceinline__ void tree_l_doc(
     for (int ph = 0; ph < 16; ph++) tprof[(size_t)d * 16 + ph] = tacc[ph];
 }
 
-template <int NT, int TILE_T, bool PROF, int MODE>
+template <int NT, int TILE_T, bool PROF>
 __global__ __launch_bounds__(NT) void k_tree_l(
     const uint32_t *__restrict__ par, const uint8_t *__restrict__ skind,
     const uint32_t *__restrict__ doc_off, const uint32_t *__restrict__ doc_log2k, uint32_t kbits,
@@ -2360,8 +2356,8 @@ __global__ __launch_bounds__(NT) void k_tree_l(
     unsigned long long *__restrict__ tprof,
     const uint32_t *__restrict__ kbm, const uint32_t *__restrict__ tile_first, uint32_t doc0 = 0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_tl[];
-  tree_l_doc<NT, TILE_T, PROF, MODE>(par, skind, doc_off, doc_log2k, kbits, bm_words, nsc, fcS, link,
-                                     osp, tprof, kbm, tile_first, doc0 + blockIdx.x, lds_tl);
+  tree_l_doc<NT, TILE_T, PROF>(par, skind, doc_off, doc_log2k, kbits, bm_words, nsc, fcS, link, osp,
+                               tprof, kbm, tile_first, doc0 + blockIdx.x, lds_tl);
 }
 
 // --- tree for one giant document (all tiles in parallel) -------------------------
@@ -3494,7 +3490,7 @@ __global__ __launch_bounds__(NT) void k_tour(const uint32_t *__restrict__ link,
 // there is one tail instead of three.  A document whose ids leave the front
 // end's directory counts itself in big[0] and stops: the host then weaves the
 // batch with the separate kernels.
-template <int NT, int TILE_T, typename VT, bool PROF, int TLM = 0, int FV = 0>
+template <int NT, int TILE_T, typename VT, bool PROF>
 __global__ __launch_bounds__(NT) void k_weave_doc(
     const uint64_t *__restrict__ id_key, const uint64_t *__restrict__ cause_key,
     const uint8_t *__restrict__ kind, const uint32_t *__restrict__ doc_off,
@@ -3511,19 +3507,19 @@ __global__ __launch_bounds__(NT) void k_weave_doc(
   const uint32_t d = blockIdx.x;
   // (tprof, tree_prof: the three phases' clocks per document)
   const unsigned long long t0 = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
-  // FV (CW_FRONT_U): items in flight per thread in the front end's directory
-  // and input-index passes (1: 16, 0: 4 as in k_front); the rank pass loads
-  // and ranks 6 items a thread in turn (round 5: 4 double-buffered, 12.17 ->
-  // 12.11 ms a config-2 step; 8 spill)
-  constexpr uint32_t U1 = FV == 0 ? 4 : 16, U2 = 6, U3 = U1;
+  // items in flight per thread: 16 in the front end's directory and
+  // input-index passes (k_front keeps 4); the rank pass loads and ranks 6
+  // items a thread in turn (round 5: 4 double-buffered, 12.17 -> 12.11 ms a
+  // config-2 step; 8 spill)
+  constexpr uint32_t U1 = 16, U2 = 6, U3 = 16;
   if (!front_doc<NT, uint16_t, VT, U1, U2, U3>(id_key, cause_key, kind, doc_off, tile_first, sg, par, skind, sval, kbm, skey,
                      rank16, max_ts, ts_shift, status, big, nullptr, d,
                      reinterpret_cast<uint4 *>(lds_w), site8, site_shift, site_mask))
     return;
   __syncthreads();  // (workgroup-scope release/acquire: this CU's writes are visible to it)
   const unsigned long long t1 = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
-  tree_l_doc<NT, TILE_T, false, TLM, uint16_t>(par, skind, doc_off, doc_log2k, kbits, bm_words, nsc, fcS, link,
-                                   osp, nullptr, kbm, tile_first, d, lds_w);
+  tree_l_doc<NT, TILE_T, false, uint16_t>(par, skind, doc_off, doc_log2k, kbits, bm_words, nsc, fcS, link,
+                                          osp, nullptr, kbm, tile_first, d, lds_w);
   __syncthreads();
   const unsigned long long t2 = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
   tour_doc<NT, VT>(link, sval, doc_off, doc_log2k, nullptr, 0u, nullptr, perm, vbits, vcount, status,
@@ -5008,6 +5004,383 @@ int ensure_tables(cw_ctx *c, uint64_t D, const uint64_t *off, bool force_giant =
   return 0;
 }
 
+// The phase stamps of a tree_prof run: `count` records (documents or packs) of
+// `stride` clocks each, in the scratch buffer `name`, zeroed on the stream.
+int alloc_stamps(cw_ctx *c, const char *name, uint64_t count, int stride, unsigned long long **tprof) {
+  *tprof = scratch_t<unsigned long long>(c, name, (size_t)count * stride);
+  if (!*tprof) return fail(c, "out of device memory (tprof)");
+  HIPCHK(c, hipMemsetAsync(*tprof, 0, (size_t)count * stride * 8, c->stream));
+  return 0;
+}
+
+// ... and their sum over the records: the first `phases` of each record's
+// `stride` clocks (waits for the stream).
+int read_stamps(cw_ctx *c, const unsigned long long *tprof, uint64_t count, int stride, int phases,
+                double *acc) {
+  std::vector<unsigned long long> h((size_t)count * stride);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h.data(), tprof, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int ph = 0; ph < phases; ph++) acc[ph] = 0;
+  for (uint64_t i = 0; i < count; i++)
+    for (int ph = 0; ph < phases; ph++) acc[ph] += (double)h[i * stride + ph];
+  return 0;
+}
+
+// One call of weave_tail: its arguments, and the scratch and tables its stages share.
+struct Tail {
+  cw_ctx *c;
+  uint64_t D;
+  uint32_t N;
+  bool giant;
+  const uint32_t *par;
+  const uint8_t *skind;
+  const uint32_t *sval, *kbm;
+  const uint64_t *skey;
+  uint32_t ts_shift;
+  cw_list_result *out;
+  void *spareA, *spareB;
+  bool linked;
+  bool hbm_walk;  // walk, rank and emit through HBM (the fused tour keeps its sublists in LDS)
+  uint32_t *nsc, *fcS, *fcN;  // node arrays
+  uint64_t *link;             // u32 or u64 links; room for the yarn sort
+  uint32_t *thr;
+  uint8_t *vis8;
+  uint32_t *slots, *dyn_ctr, *wcnt, *wnext, *sbase, *order;  // the HBM walk's sublist buffers
+  uint32_t *doc_off, *doc_log2k, *doc_W, *walk_first;        // device tables
+};
+
+// 3-5 for one giant document (all tiles in parallel): effective parents,
+// sibling order (tile-local links + a sort of the cross children, or one sort
+// of every group key), threads and links.
+int tail_tree_giant(const Tail &w) {
+  cw_ctx *c = w.c;
+  const uint32_t N = w.N;
+  const dim3 B256(256);
+  const uint32_t gbits = ceil_log2(2ull * N + 2);
+  const uint32_t root_key = gbits >= 32 ? 0xFFFFFFFFu : (1u << gbits) - 1;
+  // group keys: sort input in thr (written only after the sort), ping-pong
+  // pairs in the spare buffers when the caller has them
+  uint32_t *gk = w.thr, *gkA, *gvA, *gkB, *gvB;
+  if (w.spareA && w.spareB) {
+    gkA = (uint32_t *)w.spareA;
+    gvA = gkA + N;
+    gkB = (uint32_t *)w.spareB;
+    gvB = gkB + N;
+  } else {
+    gkA = scratch_t<uint32_t>(c, "g_keyA", N), gkB = scratch_t<uint32_t>(c, "g_keyB", N);
+    gvA = scratch_t<uint32_t>(c, "g_valA", N), gvB = scratch_t<uint32_t>(c, "g_valB", N);
+  }
+  const dim3 GN((N + 255) / 256);
+  const bool glocal = N >= c->glocal_min;
+  const uint32_t TL = (N + GL_TILE - 1) / GL_TILE;
+  uint32_t *tcnt = glocal ? scratch_t<uint32_t>(c, "gl_tcnt", (size_t)TL + 1) : nullptr;
+  if (!gkA || !gkB || !gvA || !gvB || !gk || (glocal && !tcnt))
+    return fail(c, "out of device memory (giant tree)");
+  if (glocal) HIPCHK(c, hipMemsetAsync(tcnt, 0, ((size_t)TL + 1) * 4, c->stream));
+  {
+    Launch L(c, "geff", (double)N * (4 + 1 + 4) + (glocal ? 0.0 : (double)N * 8));
+    // (the walk's counter and the emit's rendered count zeroed here)
+    hipLaunchKernelGGL(k_geff, GN, B256, 0, c->stream, w.par, w.skind, N, root_key, gk, w.fcS, w.fcN,
+                       w.hbm_walk ? w.dyn_ctr : nullptr, w.out->visible_count, tcnt);
+  }
+  if (check_launch(c, "geff")) return -1;
+  if (glocal) {
+    // cross children's offsets: an exclusive scan of the tile counts in place
+    // (the sort's chunked scan with one bin)
+    const uint32_t nc = (TL + GSCAN_CHUNK - 1) / GSCAN_CHUNK;
+    uint32_t *cs = scratch_t<uint32_t>(c, "gl_cs", (size_t)nc + 1);
+    uint32_t *aux = scratch_t<uint32_t>(c, "gl_aux", 4);
+    if (!cs || !aux) return fail(c, "out of device memory (giant tree)");
+    uint32_t *mtot = aux + 1;
+    {
+      Launch L(c, "glocal", (double)N * (4 + 4 + 8 + 4 + 8 * 0.34));
+      hipLaunchKernelGGL(k_gscan_colsum, dim3(nc), dim3(1024), 0, c->stream, tcnt, TL, 1u, cs);
+      hipLaunchKernelGGL(k_gscan_chunks, dim3(1), dim3(1024), 0, c->stream, cs, nc, 1u, aux);
+      hipLaunchKernelGGL(k_gscan_bins, dim3(1), dim3(1024), 0, c->stream, aux, 1u, 0u);
+      hipLaunchKernelGGL(k_gscan_apply, dim3(nc), dim3(1024), 0, c->stream, tcnt, TL, 1u, cs, aux);
+      hipLaunchKernelGGL(k_glocal<512>, dim3(TL), dim3(512), 0, c->stream, gk, N, tcnt, w.nsc, w.fcS,
+                         w.fcN, gkA, gvA, mtot);
+    }
+    if (check_launch(c, "glocal")) return -1;
+    // the cross children's count sizes their sort (one readback)
+    if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+    HIPCHK(c, hipMemcpyAsync(c->pin_small, mtot, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t M = c->pin_small[0];
+    if (M > N) return fail(c, "cross children %u > %u", M, N);
+    if (M) {
+      const uint32_t TR = (M + TILE - 1) / TILE;
+      std::vector<uint32_t> h((size_t)TR + 1 + TR + 2 + 2);
+      for (uint32_t i = 0; i <= TR; i++) h[i] = std::min(i * TILE, M);  // tile_start
+      for (uint32_t i = 0; i < TR; i++) h[TR + 1 + i] = 0;                // tile_doc
+      h[2 * TR + 1] = 0, h[2 * TR + 2] = M;                               // doc_off
+      h[2 * TR + 3] = 0, h[2 * TR + 4] = TR;                              // tile_first
+      uint32_t *dt = scratch_t<uint32_t>(c, "gl_rtab", h.size());
+      if (!dt) return fail(c, "out of device memory (giant tree)");
+      HIPCHK(c, hipMemcpy(dt, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+      const RSTab rt{TR, 1u, dt, dt + TR + 1, dt + 2 * TR + 1, dt + 2 * TR + 3};
+      uint32_t *gks, *gvs;  // (ping-pong through the input pair itself)
+      if (radix_sort<uint32_t>(c, "gsort", gkA, gvA, gkB, gvB, gkA, gvA, gbits, 0, M, &gks, &gvs,
+                               nullptr, nullptr, &rt))
+        return -1;
+      {
+        Launch L(c, "gcross", (double)M * (8 + 4 + 4 + 8));
+        const dim3 GM((M + 255) / 256);
+        hipLaunchKernelGGL(k_gcross_ns, GM, B256, 0, c->stream, gks, gvs, mtot, w.nsc, w.fcS, w.fcN);
+        hipLaunchKernelGGL(k_gcross_fc, GM, B256, 0, c->stream, gks, gvs, mtot, w.fcS, w.fcN);
+      }
+      if (check_launch(c, "gcross")) return -1;
+    }
+  } else {
+    uint32_t *gks, *gvs;
+    if (radix_sort<uint32_t>(c, "gsort", gk, nullptr, gkA, gvA, gkB, gvB, gbits, 0, N, &gks, &gvs))
+      return -1;
+    {
+      Launch L(c, "gsib", (double)N * (4 + 4 + 4 + 4));
+      hipLaunchKernelGGL(k_gsib, GN, B256, 0, c->stream, gks, gvs, N, w.nsc, w.fcS, w.fcN);
+    }
+    if (check_launch(c, "gsib")) return -1;
+  }
+  {
+    Launch L(c, "gthr", (double)N * (4 + 4 + 4 + 1 + 4 + 4));
+    hipLaunchKernelGGL((k_gthr<256, 1024>), dim3((N + 1023) / 1024), B256, 0, c->stream, w.nsc,
+                       w.fcS, w.fcN, w.skind, N, w.sval, w.thr, w.link);
+  }
+  return check_launch(c, "gthr");
+}
+
+// 3-5 per document, one workgroup each: k_tree_l (sibling groups in LDS) where
+// the document's tables fit, k_tree otherwise.
+int tail_tree_docs(const Tail &w) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  const uint64_t D = w.D;
+  const uint32_t kbits = ceil_log2((uint64_t)t.nmax + 1) + 1;
+  // special/hide bitmaps in LDS for documents up to 2^18 nodes
+  const uint32_t bm_words = std::min<uint32_t>((t.nmax + 31) / 32, (1u << 18) / 32);
+  // par, skind in; nsc, last-node tables, thr, link out; sweep 2 reads nsc
+  // and the tables back
+  unsigned long long *tprof = nullptr;
+  if (c->tree_prof && alloc_stamps(c, "tprof", D, 16, &tprof)) return -1;
+  constexpr uint32_t TL_NT = 1024;
+  const uint32_t tl_dyn = tree_l_lds_bytes(t.nmax);
+  // k_tree_l with 2,048-rank tiles, or 1,024 when the document needs the room
+  const uint32_t tree_l = !c->tree_l ? 0
+                          : c->tree_l == 2048 && tl_dyn + tree_l_static_bytes(TL_NT, 2048) <= c->lds_max ? 2048
+                          : tl_dyn + tree_l_static_bytes(TL_NT, 1024) <= c->lds_max ? 1024 : 0;
+  {
+    // k_tree_l: par 4 + kind bits in; fcS clear 4, nsc 4 out; sweep 2 reads
+    // fcS, nsc (8) and writes link 4
+    Launch L(c, "tree", tree_l ? (double)w.N * (4 + 1 + 4 + 4 + 8 + 4)
+                               : (double)w.N * (4 + 1 + 4 + 8 + 4 + 8 + 4 + 4));
+    if (tree_l) {
+      auto *kern = tprof ? (tree_l == 2048 ? k_tree_l<TL_NT, 2048, true> : k_tree_l<TL_NT, 1024, true>)
+                         : (tree_l == 2048 ? k_tree_l<TL_NT, 2048, false> : k_tree_l<TL_NT, 1024, false>);
+      hipLaunchKernelGGL(kern, dim3((uint32_t)D), dim3(TL_NT),
+                         (size_t)tl_dyn + tree_l_tile_bytes(TL_NT, tree_l), c->stream, w.par, w.skind,
+                         w.doc_off, w.doc_log2k, kbits, (t.nmax + 31) / 32, w.nsc, w.fcS,
+                         (uint32_t *)w.link, w.thr, tprof, w.kbm, dev_tab(c, "t_tile_first"), 0u);
+    } else
+      hipLaunchKernelGGL((k_tree<256, 1024>), dim3((uint32_t)D), dim3(256), (size_t)bm_words * 8,
+                         c->stream, w.par, w.skind, w.doc_off, w.doc_log2k, kbits, bm_words, w.nsc,
+                         w.fcS, w.fcN, w.thr, (uint32_t *)w.link, w.out->status, tprof, w.kbm,
+                         dev_tab(c, "t_tile_first"));
+  }
+  if (check_launch(c, "tree")) return -1;
+  if (tprof) {
+    double acc[16];
+    if (read_stamps(c, tprof, D, 16, 16, acc)) return -1;
+    // k_tree: bitmap climb sort prv s2load jump s2write; k_tree_l: bitmap barA . end
+    // s2init s2calc jump s2write head keys issue insert walk barB
+    fprintf(stderr, "tree phases (memtime ticks per doc):");
+    for (int ph = 0; ph < 16; ph++) fprintf(stderr, " %d:%.0f", ph, acc[ph] / D);
+    fprintf(stderr, "\n");
+  }
+  return 0;
+}
+
+// 6-8. walk, rank and emit of every document in LDS (and the bitmap)
+int tail_tour(const Tail &w) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  cw_list_result *out = w.out;
+  const uint64_t D = w.D;
+  unsigned long long *tprof = nullptr;
+  if (c->tree_prof && alloc_stamps(c, "tprof2", D, 8, &tprof)) return -1;
+  uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", w.N);
+  if (!loc) return fail(c, "out of device memory (tour)");
+  {
+    Launch L(c, "tour", (double)w.N * (4 + 4 + 4 + 1 + 4 + 4));
+    hipLaunchKernelGGL(k_tour<1024>, dim3((uint32_t)D), dim3(1024),
+                       (size_t)tour_lds_bytes(t.nmax, t.tour_log2k), c->stream,
+                       (const uint32_t *)w.link, w.sval, w.doc_off, w.doc_log2k, w.skey, w.ts_shift,
+                       w.skey ? out->max_ts : nullptr, out->weave_perm, out->visible_bits,
+                       out->visible_count, out->status, loc, tprof);
+  }
+  if (check_launch(c, "tour")) return -1;
+  if (tprof) {
+    double a[5];
+    if (read_stamps(c, tprof, D, 8, 5, a)) return -1;
+    fprintf(stderr, "tour phases (memtime ticks per doc): load %.0f walk %.0f jump %.0f place %.0f "
+            "write %.0f\n", a[0] / D, a[1] / D, a[2] / D, a[3] / D, a[4] / D);
+  }
+  return 0;
+}
+
+// 6. walk: sublists of the preorder successor list
+int tail_walk(const Tail &w) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  const uint64_t D = w.D;
+  if (!(w.giant && !w.linked)) HIPCHK(c, hipMemsetAsync(w.dyn_ctr, 0, D * 4, c->stream));  // (k_geff did)
+  c->last_dyn = w.dyn_ctr;  // (cw_get_counter "continued_sublists")
+  c->last_dyn_n = (uint32_t)D;
+  unsigned long long *wprof = nullptr;
+  if (c->tree_prof && w.giant) {
+    wprof = scratch_t<unsigned long long>(c, "wprof", 4);
+    HIPCHK(c, hipMemsetAsync(wprof, 0, 32, c->stream));
+  }
+  {
+    Launch L(c, "walk", (double)w.N * (4 + 4));
+    hipLaunchKernelGGL(w.giant ? k_walk<true> : k_walk<false>, dim3(t.Bw), dim3(c->walk_threads),
+                       0, c->stream, (const void *)w.link, w.thr,
+                       dev_tab(c, "t_wblk_doc"), dev_tab(c, "t_wblk_w0"), w.doc_off, w.doc_log2k,
+                       dev_tab(c, "t_doc_log2cap"), w.doc_W, dev_tab(c, "t_doc_Wcap"), w.walk_first,
+                       (const uint64_t *)c->bufs["t_slot_first"].p, w.slots, w.wcnt, w.wnext, w.dyn_ctr,
+                       w.out->status, c->walk_span, wprof);
+  }
+  if (check_launch(c, "walk")) return -1;
+  if (wprof) {
+    unsigned long long h[4];
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(h, wprof, 32, hipMemcpyDeviceToHost));
+    fprintf(stderr, "walk profile: nodes %u steps %llu pending %llu thread hops %llu\n", w.N, h[0], h[1],
+            h[2]);
+  }
+  return 0;
+}
+
+// The giant ranking's walk levels over Ws walkers (E entries at the sublist
+// level): K = 16, until the walkers fit one LDS ranking; the last level takes
+// a longer stride (<= 64) instead of one more level of launches.  Offsets are
+// uint32 words of one scratch buffer (16-byte units); nbt_off: the top
+// ranking's tables; words: the buffer's size.
+struct RankLevel { uint32_t E, Ws, K, S; size_t pos, wout, base; };
+struct RankPlan { std::vector<RankLevel> lv; size_t nbt_off, words; };
+RankPlan plan_rank_levels(uint32_t E, uint32_t Ws) {
+  RankPlan p;
+  auto &lv = p.lv;
+  size_t words = 0;
+  while (lv.empty() || lv.back().S > SUP_MAX) {
+    const uint32_t need = (Ws + SUP_MAX - 1) / SUP_MAX;
+    uint32_t K = 16;
+    if (need <= 64) {
+      K = 1;
+      while (K < need) K <<= 1;
+    }
+    RankLevel v{E, Ws, K, (Ws + K - 1) / K, 0, 0, 0};
+    v.pos = words, words += lv.empty() ? 0 : 4 * (size_t)v.E;  // (sublist level: none)
+    v.wout = words, words += 4 * (size_t)v.S;
+    v.base = words, words += lv.empty() ? 0 : 4 * (((size_t)v.E + 1) / 2);
+    lv.push_back(v);
+    E = Ws = v.S;
+  }
+  p.nbt_off = words;
+  p.words = words + 2 * (size_t)lv.back().S + 4;
+  return p;
+}
+
+// 7 for one giant document: the sublists' ranks and bases into erec
+int tail_rank_giant(const Tail &w, uint4 **erec_out) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  cw_list_result *out = w.out;
+  const uint32_t N = w.N;
+  const dim3 B256(256);
+  uint32_t *const wcnt = w.wcnt, *const dyn_ctr = w.dyn_ctr;
+  // the walkers the walk added (pending threads) stay on the device: the
+  // ranking kernels read W + dyn_ctr[0] themselves, no readback (sync) here
+  const uint32_t W = t.doc_W[0], Wcap = t.Wtot;
+  const uint64_t *wl = reinterpret_cast<const uint64_t *>(wcnt);  // k_walk<true>'s words
+  uint4 *erec = *erec_out = scratch_t<uint4>(c, "g_erec", Wcap);
+  if (!erec) return fail(c, "out of device memory (rank)");
+  if (Wcap <= SUP_MAX) {  // few sublists: one LDS ranking, no walk levels
+    uint32_t *nbt = scratch_t<uint32_t>(c, "g_nbt", 2 * (size_t)Wcap);
+    if (!nbt) return fail(c, "out of device memory (rank)");
+    Launch L(c, "rank", (double)Wcap * 36);
+    hipLaunchKernelGGL(k_sup_rank, dim3(1), dim3(1024), (size_t)Wcap * 12, c->stream, wcnt, nullptr,
+                       wcnt + 1, 2u, Wcap, N, Wcap, nbt, nbt + Wcap, out->status, nullptr, dyn_ctr, W,
+                       Wcap);
+    hipLaunchKernelGGL(k_lvl_apply, dim3((Wcap + 255) / 256), B256, 0, c->stream, nullptr, nbt,
+                       nbt + Wcap, nullptr, wl, Wcap, nullptr, erec, dyn_ctr, W);
+    return 0;
+  }
+  const RankPlan plan = plan_rank_levels(Wcap, W);
+  const std::vector<RankLevel> &lv = plan.lv;
+  uint32_t *lb = scratch_t<uint32_t>(c, "g_levels", plan.words);
+  if (!lb) return fail(c, "out of device memory (multi-level rank)");
+  auto u4 = [&](size_t o) { return reinterpret_cast<uint4 *>(lb + o); };
+  auto u2 = [&](size_t o) { return reinterpret_cast<uint2 *>(lb + o); };
+  Launch L(c, "rank", (double)Wcap * 40 + (double)lv[0].S * 40);
+  for (size_t i = 0; i < lv.size(); i++) {  // up: every level's walkers over the one below
+    const RankLevel &v = lv[i];
+    if (i == 0)  // (no per-sublist records: k_lvl_emit walks again)
+      hipLaunchKernelGGL(k_lvl_walk<true>, dim3((v.S + 255) / 256), B256, 0, c->stream,
+                         (const void *)wl, v.Ws, v.E, v.K, v.S, nullptr, u4(v.wout), out->status,
+                         dyn_ctr, W);
+    else
+      hipLaunchKernelGGL(k_lvl_walk<false>, dim3((v.S + 255) / 256), B256, 0, c->stream,
+                         (const void *)u4(lv[i - 1].wout), v.Ws, v.E, v.K, v.S, u4(v.pos),
+                         u4(v.wout), out->status, nullptr, 0u);
+  }
+  const RankLevel &top = lv.back();
+  uint32_t *nb = lb + plan.nbt_off, *tb = nb + top.S;
+  const uint32_t *tw = lb + top.wout;
+  hipLaunchKernelGGL(k_sup_rank, dim3(1), dim3(1024), (size_t)top.S * 12, c->stream, tw, tw + 1,
+                     tw + 2, 4u, top.S, N, Wcap, nb, tb, out->status, nullptr, dyn_ctr, W, Wcap);
+  for (size_t i = lv.size(); i-- > 0;) {  // down: the ranks applied level by level
+    const RankLevel &v = lv[i];
+    const bool is_top = i + 1 == lv.size();
+    const uint2 *bq = is_top ? nullptr : u2(lv[i + 1].base);
+    if (i == 0) {
+      hipLaunchKernelGGL(k_lvl_emit, dim3((v.S + 255) / 256), B256, 0, c->stream, wl, v.Ws, v.E, v.K,
+                         v.S, nb, tb, bq, erec, dyn_ctr, W);
+    } else
+      hipLaunchKernelGGL(k_lvl_apply, dim3((v.E + 255) / 256), B256, 0, c->stream, u4(v.pos), nb,
+                         tb, bq, nullptr, v.E, u2(v.base), nullptr, nullptr, 0u);
+  }
+  return 0;
+}
+
+// 7-8. rank sublists (+ max lamport-ts per document), emit
+int tail_emit(const Tail &w) {
+  cw_ctx *c = w.c;
+  auto &t = c->tab;
+  cw_list_result *out = w.out;
+  const dim3 B256(256);
+  uint4 *erec = nullptr;
+  if (w.giant) {
+    if (tail_rank_giant(w, &erec)) return -1;
+  } else {
+    Launch L(c, "rank", (double)t.Wtot * 12);
+    hipLaunchKernelGGL(k_rank, dim3((uint32_t)w.D), B256, (size_t)t.Wmax * 8, c->stream, w.wcnt,
+                       w.wnext, w.walk_first, w.doc_W, w.dyn_ctr, w.doc_off, w.skey, w.ts_shift,
+                       w.sbase, w.order, w.skey ? out->max_ts : nullptr, out->status);
+  }
+  if (check_launch(c, "rank")) return -1;
+  {
+    Launch L(c, "emit", (double)w.N * (4 + 4 + 4 + 1) + (double)t.Wtot * 8);
+    // (giant: the slot entries hold the emitted values already, see k_walk)
+    hipLaunchKernelGGL(k_emit, dim3(t.Be), B256, 0, c->stream, w.slots,
+                       (const uint64_t *)c->bufs["t_slot_first"].p, w.wcnt, w.sbase, w.order,
+                       w.giant ? nullptr : w.sval, erec,
+                       dev_tab(c, "t_eblk_doc"), dev_tab(c, "t_eblk_x0"), w.walk_first, w.doc_W,
+                       w.dyn_ctr, dev_tab(c, "t_doc_log2cap"), w.doc_off, out->weave_perm, w.vis8,
+                       out->visible_count, out->status);
+  }
+  return check_launch(c, "emit");
+}
+
 // Steps 3-9 of the list weave from the rank-ordered arrays: par (cause rank),
 // skind, sval (the value emitted for each rank; nullptr = the rank itself).
 // skey != nullptr: ::lamport-ts from the largest sorted id (otherwise the
@@ -5019,356 +5392,53 @@ int weave_tail(cw_ctx *c, uint64_t D, uint32_t N, bool giant, const uint32_t *pa
                const uint64_t *skey, uint32_t ts_shift, cw_list_result *out,
                void *spareA = nullptr, void *spareB = nullptr, bool linked = false) {
   auto &t = c->tab;
-  const dim3 B256(256);
   if (giant && out->max_ts && skey) {  // ::lamport-ts = largest id (k_fdir wrote it otherwise)
     hipLaunchKernelGGL(k_max_ts1, dim3(1), dim3(64), 0, c->stream, skey, N, ts_shift, out->max_ts);
     if (check_launch(c, "max_ts")) return -1;
   }
-  uint32_t *nsc = scratch_t<uint32_t>(c, "nsc", N);
-  uint32_t *fcS = scratch_t<uint32_t>(c, "fcS", N), *fcN = scratch_t<uint32_t>(c, "fcN", N);
-  uint64_t *link = scratch_t<uint64_t>(c, "link", N);  // u32 or u64 links; room for the yarn sort
-  uint32_t *thr = scratch_t<uint32_t>(c, "thr", N);
-  uint8_t *vis8 = scratch_t<uint8_t>(c, "vis8", (size_t)N + 64);
-  if (!nsc || !fcS || !fcN || !link || !thr || !vis8)
+  Tail w{c, D, N, giant, par, skind, sval, kbm, skey, ts_shift, out, spareA, spareB, linked};
+  w.nsc = scratch_t<uint32_t>(c, "nsc", N);
+  w.fcS = scratch_t<uint32_t>(c, "fcS", N), w.fcN = scratch_t<uint32_t>(c, "fcN", N);
+  w.link = scratch_t<uint64_t>(c, "link", N);
+  w.thr = scratch_t<uint32_t>(c, "thr", N);
+  w.vis8 = scratch_t<uint8_t>(c, "vis8", (size_t)N + 64);
+  if (!w.nsc || !w.fcS || !w.fcN || !w.link || !w.thr || !w.vis8)
     return fail(c, "out of device memory (N=%u)", N);
-  // the HBM walk's sublist buffers (the fused tour keeps its sublists in LDS)
-  const bool hbm_walk = !(t.tour && !giant);
-  uint32_t *slots = nullptr, *dyn_ctr = nullptr, *wcnt = nullptr, *wnext = nullptr,
-           *sbase = nullptr, *order = nullptr;
-  if (hbm_walk) {
+  w.hbm_walk = !(t.tour && !giant);
+  if (w.hbm_walk) {
     c->last_dyn = nullptr;  // (cw_weave_ranked and the like start here: dyn_ctr may move)
     c->last_dyn_n = 0;
-    slots = scratch_t<uint32_t>(c, "slots", t.slots);
-    dyn_ctr = scratch_t<uint32_t>(c, "dyn_ctr", D);
+    w.slots = scratch_t<uint32_t>(c, "slots", t.slots);
+    w.dyn_ctr = scratch_t<uint32_t>(c, "dyn_ctr", D);
     // (one giant document: u64 {count, next} words, see k_walk)
-    wcnt = scratch_t<uint32_t>(c, "wcnt", (giant ? 2 : 1) * (size_t)t.Wtot);
-    wnext = scratch_t<uint32_t>(c, "wnext", t.Wtot);
-    sbase = scratch_t<uint32_t>(c, "sbase", t.Wtot);
-    order = scratch_t<uint32_t>(c, "order", t.Wtot);
-    if (!slots || !dyn_ctr || !wcnt || !wnext || !sbase || !order)
+    w.wcnt = scratch_t<uint32_t>(c, "wcnt", (giant ? 2 : 1) * (size_t)t.Wtot);
+    w.wnext = scratch_t<uint32_t>(c, "wnext", t.Wtot);
+    w.sbase = scratch_t<uint32_t>(c, "sbase", t.Wtot);
+    w.order = scratch_t<uint32_t>(c, "order", t.Wtot);
+    if (!w.slots || !w.dyn_ctr || !w.wcnt || !w.wnext || !w.sbase || !w.order)
       return fail(c, "out of device memory (walk, N=%u)", N);
   }
-  uint32_t *doc_off = dev_tab(c, "t_doc_off"), *doc_log2k = dev_tab(c, "t_doc_log2k");
-  uint32_t *doc_W = dev_tab(c, "t_doc_W"), *walk_first = dev_tab(c, "t_walk_first");
+  w.doc_off = dev_tab(c, "t_doc_off"), w.doc_log2k = dev_tab(c, "t_doc_log2k");
+  w.doc_W = dev_tab(c, "t_doc_W"), w.walk_first = dev_tab(c, "t_walk_first");
   // 3-5. effective parents, sibling order, links (linked: the caller wrote
   // link and thr, cw_weave_linked)
-  if (giant && !linked) {
-    const uint32_t gbits = ceil_log2(2ull * N + 2);
-    const uint32_t root_key = gbits >= 32 ? 0xFFFFFFFFu : (1u << gbits) - 1;
-    // group keys: sort input in thr (written only after the sort), ping-pong
-    // pairs in the spare buffers when the caller has them
-    uint32_t *gk = thr, *gkA, *gvA, *gkB, *gvB;
-    if (spareA && spareB) {
-      gkA = (uint32_t *)spareA;
-      gvA = gkA + N;
-      gkB = (uint32_t *)spareB;
-      gvB = gkB + N;
-    } else {
-      gkA = scratch_t<uint32_t>(c, "g_keyA", N), gkB = scratch_t<uint32_t>(c, "g_keyB", N);
-      gvA = scratch_t<uint32_t>(c, "g_valA", N), gvB = scratch_t<uint32_t>(c, "g_valB", N);
-    }
-    if (!gkA || !gkB || !gvA || !gvB || !gk) return fail(c, "out of device memory (giant tree)");
-    const dim3 GN((N + 255) / 256);
-    const bool glocal = N >= c->glocal_min;
-    const uint32_t TL = (N + GL_TILE - 1) / GL_TILE;
-    uint32_t *tcnt = nullptr;
-    if (glocal) {
-      tcnt = scratch_t<uint32_t>(c, "gl_tcnt", (size_t)TL + 1);
-      if (!tcnt) return fail(c, "out of device memory (giant tree)");
-      HIPCHK(c, hipMemsetAsync(tcnt, 0, ((size_t)TL + 1) * 4, c->stream));
-    }
-    {
-      Launch L(c, "geff", (double)N * (4 + 1 + 4) + (glocal ? 0.0 : (double)N * 8));
-      // (the walk's counter and the emit's rendered count zeroed here)
-      hipLaunchKernelGGL(k_geff, GN, B256, 0, c->stream, par, skind, N, root_key, gk, fcS, fcN,
-                         hbm_walk ? dyn_ctr : nullptr, out->visible_count, tcnt);
-    }
-    if (check_launch(c, "geff")) return -1;
-    if (glocal) {
-      // cross children's offsets: an exclusive scan of the tile counts in place
-      // (the sort's chunked scan with one bin)
-      const uint32_t nc = (TL + GSCAN_CHUNK - 1) / GSCAN_CHUNK;
-      uint32_t *cs = scratch_t<uint32_t>(c, "gl_cs", (size_t)nc + 1);
-      uint32_t *aux = scratch_t<uint32_t>(c, "gl_aux", 4);
-      if (!cs || !aux) return fail(c, "out of device memory (giant tree)");
-      uint32_t *mtot = aux + 1;
-      {
-        Launch L(c, "glocal", (double)N * (4 + 4 + 8 + 4 + 8 * 0.34));
-        hipLaunchKernelGGL(k_gscan_colsum, dim3(nc), dim3(1024), 0, c->stream, tcnt, TL, 1u, cs);
-        hipLaunchKernelGGL(k_gscan_chunks, dim3(1), dim3(1024), 0, c->stream, cs, nc, 1u, aux);
-        hipLaunchKernelGGL(k_gscan_bins, dim3(1), dim3(1024), 0, c->stream, aux, 1u, 0u);
-        hipLaunchKernelGGL(k_gscan_apply, dim3(nc), dim3(1024), 0, c->stream, tcnt, TL, 1u, cs, aux);
-        hipLaunchKernelGGL(k_glocal<512>, dim3(TL), dim3(512), 0, c->stream, gk, N, tcnt, nsc, fcS, fcN,
-                           gkA, gvA, mtot);
-      }
-      if (check_launch(c, "glocal")) return -1;
-      // the cross children's count sizes their sort (one readback)
-      if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-      HIPCHK(c, hipMemcpyAsync(c->pin_small, mtot, 4, hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      const uint32_t M = c->pin_small[0];
-      if (M > N) return fail(c, "cross children %u > %u", M, N);
-      if (M) {
-        const uint32_t TR = (M + TILE - 1) / TILE;
-        std::vector<uint32_t> h((size_t)TR + 1 + TR + 2 + 2);
-        for (uint32_t i = 0; i <= TR; i++) h[i] = std::min(i * TILE, M);  // tile_start
-        for (uint32_t i = 0; i < TR; i++) h[TR + 1 + i] = 0;                // tile_doc
-        h[2 * TR + 1] = 0, h[2 * TR + 2] = M;                               // doc_off
-        h[2 * TR + 3] = 0, h[2 * TR + 4] = TR;                              // tile_first
-        uint32_t *dt = scratch_t<uint32_t>(c, "gl_rtab", h.size());
-        if (!dt) return fail(c, "out of device memory (giant tree)");
-        HIPCHK(c, hipMemcpy(dt, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-        const RSTab rt{TR, 1u, dt, dt + TR + 1, dt + 2 * TR + 1, dt + 2 * TR + 3};
-        uint32_t *gks, *gvs;  // (ping-pong through the input pair itself)
-        if (radix_sort<uint32_t>(c, "gsort", gkA, gvA, gkB, gvB, gkA, gvA, gbits, 0, M, &gks, &gvs,
-                                 nullptr, nullptr, &rt))
-          return -1;
-        {
-          Launch L(c, "gcross", (double)M * (8 + 4 + 4 + 8));
-          const dim3 GM((M + 255) / 256);
-          hipLaunchKernelGGL(k_gcross_ns, GM, B256, 0, c->stream, gks, gvs, mtot, nsc, fcS, fcN);
-          hipLaunchKernelGGL(k_gcross_fc, GM, B256, 0, c->stream, gks, gvs, mtot, fcS, fcN);
-        }
-        if (check_launch(c, "gcross")) return -1;
-      }
-    } else {
-      uint32_t *gks, *gvs;
-      if (radix_sort<uint32_t>(c, "gsort", gk, nullptr, gkA, gvA, gkB, gvB, gbits, 0, N, &gks, &gvs))
-        return -1;
-      {
-        Launch L(c, "gsib", (double)N * (4 + 4 + 4 + 4));
-        hipLaunchKernelGGL(k_gsib, GN, B256, 0, c->stream, gks, gvs, N, nsc, fcS, fcN);
-      }
-      if (check_launch(c, "gsib")) return -1;
-    }
-    {
-      Launch L(c, "gthr", (double)N * (4 + 4 + 4 + 1 + 4 + 4));
-      hipLaunchKernelGGL((k_gthr<256, 1024>), dim3((N + 1023) / 1024), B256, 0, c->stream, nsc,
-                         fcS, fcN, skind, N, sval, thr, link);
-    }
-    if (check_launch(c, "gthr")) return -1;
-  }
   if (!giant) {
-    const uint32_t kbits = ceil_log2((uint64_t)t.nmax + 1) + 1;
-    // special/hide bitmaps in LDS for documents up to 2^18 nodes
-    const uint32_t bm_words = std::min<uint32_t>((t.nmax + 31) / 32, (1u << 18) / 32);
-    // par, skind in; nsc, last-node tables, thr, link out; sweep 2 reads nsc
-    // and the tables back
-    unsigned long long *tprof = nullptr;
-    if (c->tree_prof) {
-      tprof = scratch_t<unsigned long long>(c, "tprof", (size_t)D * 16);
-      HIPCHK(c, hipMemsetAsync(tprof, 0, (size_t)D * 128, c->stream));
-    }
-    constexpr uint32_t TL_NT = 1024;
-    const uint32_t tl_dyn = tree_l_lds_bytes(t.nmax);
-    // k_tree_l with 2,048-rank tiles, or 1,024 when the document needs the room
-    const uint32_t tree_l = !c->tree_l ? 0
-                            : c->tree_l == 2048 && tl_dyn + tree_l_static_bytes(TL_NT, 2048) <= c->lds_max ? 2048
-                            : tl_dyn + tree_l_static_bytes(TL_NT, 1024) <= c->lds_max ? 1024 : 0;
-    // k_tree_l: par 4 + kind bits in; fcS clear 4, nsc 4 out; sweep 2 reads
-    // fcS, nsc (8) and writes link 4
-    Launch L(c, "tree", tree_l ? (double)N * (4 + 1 + 4 + 4 + 8 + 4)
-                               : (double)N * (4 + 1 + 4 + 8 + 4 + 8 + 4 + 4));
-    auto tree_l_kernel = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3((uint32_t)D), dim3(TL_NT),
-                         (size_t)tl_dyn + tree_l_tile_bytes(TL_NT, tree_l), c->stream, par, skind,
-                         doc_off, doc_log2k, kbits, (t.nmax + 31) / 32, nsc, fcS,
-                         (uint32_t *)link, thr, tprof, kbm, dev_tab(c, "t_tile_first"), 0u);
-    };
-    auto tree_l_mode = [&](auto prof, auto mode) {
-      constexpr bool P = decltype(prof)::value;
-      constexpr int M = decltype(mode)::value;
-      if (tree_l == 2048) tree_l_kernel(k_tree_l<TL_NT, 2048, P, M>);
-      else tree_l_kernel(k_tree_l<TL_NT, 1024, P, M>);
-    };
-    auto tree_l_prof = [&](auto prof) { tree_l_mode(prof, std::integral_constant<int, 4>()); };
-    if (tree_l) {
-      if (tprof) tree_l_prof(std::true_type());
-      else tree_l_prof(std::false_type());
-    }
-    else
-      hipLaunchKernelGGL((k_tree<256, 1024>), dim3((uint32_t)D), dim3(256), (size_t)bm_words * 8,
-                         c->stream, par, skind, doc_off, doc_log2k, kbits, bm_words, nsc, fcS, fcN, thr,
-                         (uint32_t *)link, out->status, tprof, kbm, dev_tab(c, "t_tile_first"));
+    if (tail_tree_docs(w)) return -1;
+  } else if (!linked) {
+    if (tail_tree_giant(w)) return -1;
   }
-  if (check_launch(c, "tree")) return -1;
-  if (c->tree_prof && !giant) {
-    std::vector<unsigned long long> h((size_t)D * 16);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(h.data(), c->bufs["tprof"].p, (size_t)D * 128, hipMemcpyDeviceToHost));
-    double acc[16] = {0};
-    for (uint64_t d = 0; d < D; d++)
-      for (int ph = 0; ph < 16; ph++) acc[ph] += (double)h[d * 16 + ph];
-    // k_tree: bitmap climb sort prv s2load jump s2write; k_tree_l: bitmap barA . end
-    // s2init s2calc jump s2write head keys issue insert walk barB
-    fprintf(stderr, "tree phases (memtime ticks per doc):");
-    for (int ph = 0; ph < 16; ph++) fprintf(stderr, " %d:%.0f", ph, acc[ph] / D);
-    fprintf(stderr, "\n");
-  }
-
-  if (t.tour && !giant) {
-    // 6-8. walk, rank and emit of every document in LDS
-    unsigned long long *tprof = nullptr;
-    if (c->tree_prof) {
-      tprof = scratch_t<unsigned long long>(c, "tprof2", (size_t)D * 8);
-      HIPCHK(c, hipMemsetAsync(tprof, 0, (size_t)D * 64, c->stream));
-    }
-    uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", N);
-    if (!loc) return fail(c, "out of device memory (tour)");
-    {
-      Launch L(c, "tour", (double)N * (4 + 4 + 4 + 1 + 4 + 4));
-      hipLaunchKernelGGL(k_tour<1024>, dim3((uint32_t)D), dim3(1024),
-                         (size_t)tour_lds_bytes(t.nmax, t.tour_log2k), c->stream,
-                         (const uint32_t *)link, sval, doc_off, doc_log2k, skey, ts_shift,
-                         skey ? out->max_ts : nullptr, out->weave_perm, out->visible_bits,
-                         out->visible_count, out->status, loc, tprof);
-    }
-    if (check_launch(c, "tour")) return -1;
-    if (tprof) {
-      std::vector<unsigned long long> h((size_t)D * 8);
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(h.data(), tprof, (size_t)D * 64, hipMemcpyDeviceToHost));
-      double a[6] = {0};
-      for (uint64_t d = 0; d < D; d++)
-        for (int ph = 0; ph < 6; ph++) a[ph] += (double)h[d * 8 + ph];
-      fprintf(stderr, "tour phases (memtime ticks per doc): load %.0f walk %.0f jump %.0f place %.0f "
-              "write %.0f\n", a[0] / D, a[1] / D, a[2] / D, a[3] / D, a[4] / D);
-    }
-  } else {
-    // 6. walk: sublists of the preorder successor list
-    if (!(giant && !linked)) HIPCHK(c, hipMemsetAsync(dyn_ctr, 0, D * 4, c->stream));  // (k_geff did)
-    c->last_dyn = dyn_ctr;  // (cw_get_counter "continued_sublists")
-    c->last_dyn_n = (uint32_t)D;
-    unsigned long long *wprof = nullptr;
-    if (c->tree_prof && giant) {
-      wprof = scratch_t<unsigned long long>(c, "wprof", 4);
-      HIPCHK(c, hipMemsetAsync(wprof, 0, 32, c->stream));
-    }
-    {
-      Launch L(c, "walk", (double)N * (4 + 4));
-      hipLaunchKernelGGL(giant ? k_walk<true> : k_walk<false>, dim3(t.Bw), dim3(c->walk_threads),
-                         0, c->stream, (const void *)link, thr,
-                         dev_tab(c, "t_wblk_doc"), dev_tab(c, "t_wblk_w0"), doc_off, doc_log2k,
-                         dev_tab(c, "t_doc_log2cap"), doc_W, dev_tab(c, "t_doc_Wcap"), walk_first,
-                         (const uint64_t *)c->bufs["t_slot_first"].p, slots, wcnt, wnext, dyn_ctr,
-                         out->status, c->walk_span, wprof);
-    }
-    if (check_launch(c, "walk")) return -1;
-    if (wprof) {
-      unsigned long long h[4];
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(h, wprof, 32, hipMemcpyDeviceToHost));
-      fprintf(stderr, "walk profile: nodes %u steps %llu pending %llu thread hops %llu\n", N, h[0], h[1],
-              h[2]);
-    }
-
-    // 7. rank sublists (+ max lamport-ts per document)
-    uint4 *erec = nullptr;
-    if (giant) {
-      // the walkers the walk added (pending threads) stay on the device: the
-      // ranking kernels read W + dyn_ctr[0] themselves, no readback (sync) here
-      const uint32_t W = t.doc_W[0], Wcap = t.Wtot;
-      const uint64_t *wl = reinterpret_cast<const uint64_t *>(wcnt);  // k_walk<true>'s words
-      erec = scratch_t<uint4>(c, "g_erec", Wcap);
-      if (!erec) return fail(c, "out of device memory (rank)");
-      if (Wcap <= SUP_MAX) {  // few sublists: one LDS ranking, no walk levels
-        uint32_t *nbt = scratch_t<uint32_t>(c, "g_nbt", 2 * (size_t)Wcap);
-        if (!nbt) return fail(c, "out of device memory (rank)");
-        Launch L(c, "rank", (double)Wcap * 36);
-        hipLaunchKernelGGL(k_sup_rank, dim3(1), dim3(1024), (size_t)Wcap * 12, c->stream, wcnt, nullptr,
-                           wcnt + 1, 2u, Wcap, N, Wcap, nbt, nbt + Wcap, out->status, nullptr, dyn_ctr, W,
-                           Wcap);
-        hipLaunchKernelGGL(k_lvl_apply, dim3((Wcap + 255) / 256), B256, 0, c->stream, nullptr, nbt,
-                           nbt + Wcap, nullptr, wl, Wcap, nullptr, erec, dyn_ctr, W);
-      } else {
-        // levels: K = 16, until the walkers fit one LDS ranking; the last level
-        // takes a longer stride (<= 64) instead of one more level of launches
-        struct Lv { uint32_t E, Ws, K, S; size_t pos, wout, base; };
-        std::vector<Lv> lv;
-        size_t words = 0;  // (uint32 words of one scratch buffer, 16-byte units)
-        uint32_t E = Wcap, Ws = W;
-        while (lv.empty() || lv.back().S > SUP_MAX) {
-          const uint32_t need = (Ws + SUP_MAX - 1) / SUP_MAX;
-          uint32_t K = 16;
-          if (need <= 64) {
-            K = 1;
-            while (K < need) K <<= 1;
-          }
-          Lv v{E, Ws, K, (Ws + K - 1) / K, 0, 0, 0};
-          v.pos = words, words += lv.empty() ? 0 : 4 * (size_t)v.E;  // (sublist level: none)
-          v.wout = words, words += 4 * (size_t)v.S;
-          v.base = words, words += lv.empty() ? 0 : 4 * (((size_t)v.E + 1) / 2);
-          lv.push_back(v);
-          E = Ws = v.S;
-        }
-        const size_t nbt_off = words;
-        words += 2 * (size_t)lv.back().S + 4;
-        uint32_t *lb = scratch_t<uint32_t>(c, "g_levels", words);
-        if (!lb) return fail(c, "out of device memory (multi-level rank)");
-        auto u4 = [&](size_t o) { return reinterpret_cast<uint4 *>(lb + o); };
-        auto u2 = [&](size_t o) { return reinterpret_cast<uint2 *>(lb + o); };
-        Launch L(c, "rank", (double)Wcap * 40 + (double)lv[0].S * 40);
-        for (size_t i = 0; i < lv.size(); i++) {
-          const Lv &v = lv[i];
-          if (i == 0)  // (no per-sublist records: k_lvl_emit walks again)
-            hipLaunchKernelGGL(k_lvl_walk<true>, dim3((v.S + 255) / 256), B256, 0, c->stream,
-                               (const void *)wl, v.Ws, v.E, v.K, v.S, nullptr, u4(v.wout), out->status,
-                               dyn_ctr, W);
-          else
-            hipLaunchKernelGGL(k_lvl_walk<false>, dim3((v.S + 255) / 256), B256, 0, c->stream,
-                               (const void *)u4(lv[i - 1].wout), v.Ws, v.E, v.K, v.S, u4(v.pos),
-                               u4(v.wout), out->status, nullptr, 0u);
-        }
-        const Lv &top = lv.back();
-        uint32_t *nb = lb + nbt_off, *tb = nb + top.S;
-        const uint32_t *tw = lb + top.wout;
-        hipLaunchKernelGGL(k_sup_rank, dim3(1), dim3(1024), (size_t)top.S * 12, c->stream, tw, tw + 1,
-                           tw + 2, 4u, top.S, N, Wcap, nb, tb, out->status, nullptr, dyn_ctr, W, Wcap);
-        for (size_t i = lv.size(); i-- > 0;) {
-          const Lv &v = lv[i];
-          const bool is_top = i + 1 == lv.size();
-          const uint2 *bq = is_top ? nullptr : u2(lv[i + 1].base);
-          if (i == 0) {
-            hipLaunchKernelGGL(k_lvl_emit, dim3((v.S + 255) / 256), B256, 0, c->stream, wl, v.Ws, v.E, v.K,
-                               v.S, nb, tb, bq, erec, dyn_ctr, W);
-          } else
-            hipLaunchKernelGGL(k_lvl_apply, dim3((v.E + 255) / 256), B256, 0, c->stream, u4(v.pos), nb,
-                               tb, bq, nullptr, v.E, u2(v.base), nullptr, nullptr, 0u);
-        }
-      }
-      if (check_launch(c, "rank")) return -1;
-    } else {
-      Launch L(c, "rank", (double)t.Wtot * 12);
-      hipLaunchKernelGGL(k_rank, dim3((uint32_t)D), B256, (size_t)t.Wmax * 8, c->stream, wcnt,
-                         wnext, walk_first, doc_W, dyn_ctr, doc_off, skey, ts_shift, sbase,
-                         order, skey ? out->max_ts : nullptr, out->status);
-    }
-    if (check_launch(c, "rank")) return -1;
-
-    // 8. emit
-    {
-      Launch L(c, "emit", (double)N * (4 + 4 + 4 + 1) + (double)t.Wtot * 8);
-      // (giant: the slot entries hold the emitted values already, see k_walk)
-      hipLaunchKernelGGL(k_emit, dim3(t.Be), B256, 0, c->stream, slots,
-                         (const uint64_t *)c->bufs["t_slot_first"].p, wcnt, sbase, order,
-                         giant ? nullptr : sval, erec,
-                         dev_tab(c, "t_eblk_doc"), dev_tab(c, "t_eblk_x0"), walk_first, doc_W,
-                         dyn_ctr, dev_tab(c, "t_doc_log2cap"), doc_off, out->weave_perm, vis8,
-                         out->visible_count, out->status);
-    }
-    if (check_launch(c, "emit")) return -1;
-  }
-
-  // 9. visibility bitmap (the fused tour wrote it)
-  if (out->visible_bits && !(t.tour && !giant)) {
+  // 6-8. the fused tour, which writes the bitmap as well, or the HBM walk,
+  // rank and emit
+  if (!w.hbm_walk) return tail_tour(w);
+  if (tail_walk(w) || tail_emit(w)) return -1;
+  // 9. visibility bitmap
+  if (out->visible_bits) {
     const uint32_t words = (N + 31) / 32;
     Launch L(c, "packbits", (double)N + (double)words * 4);
-    hipLaunchKernelGGL(k_pack_bits, dim3((words + 255) / 256), B256, 0, c->stream, vis8, N,
+    hipLaunchKernelGGL(k_pack_bits, dim3((words + 255) / 256), dim3(256), 0, c->stream, w.vis8, N,
                        out->visible_bits);
   }
-  if (check_launch(c, "packbits")) return -1;
-
-  return 0;
+  return check_launch(c, "packbits");
 }
 
 // One call of weave_lists_device: its arguments, and the scratch and tables
@@ -5402,19 +5472,6 @@ struct Front {
   bool yarns_fused = false;  // ... and k_yarn_doc wrote the yarns: no yarn sort
 };
 
-// The phase stamps of a tree_prof run: the sum over the documents of the first
-// `phases` of each document's `stride` clocks (waits for the stream).
-int read_stamps(cw_ctx *c, const unsigned long long *tprof, uint64_t D, int stride, int phases,
-                double *acc) {
-  std::vector<unsigned long long> h((size_t)D * 8);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h.data(), tprof, (size_t)D * 64, hipMemcpyDeviceToHost));
-  for (int ph = 0; ph < phases; ph++) acc[ph] = 0;
-  for (uint64_t dd = 0; dd < D; dd++)
-    for (int ph = 0; ph < phases; ph++) acc[ph] += (double)h[dd * stride + ph];
-  return 0;
-}
-
 // Front end 1, fused per document: documents of < 2^16 nodes whose ids fit a
 // 40 KiB directory.  k_weave_doc (the whole weave in one kernel, then
 // k_yarn_doc) where every phase fits, k_front otherwise.  A document whose ids
@@ -5441,10 +5498,7 @@ int front_fused(const ListWeave &w, Front *f) {
   // written, no sort by site afterwards
   f->yarns_fused = w.want_yarns && bt->site_bits <= 4 && yarn_lds_bytes(t.nmax) + 64 <= c->lds_max;
   unsigned long long *tprof_f = nullptr;
-  if (c->tree_prof) {
-    tprof_f = scratch_t<unsigned long long>(c, "tprof3", (size_t)D * 8);
-    HIPCHK(c, hipMemsetAsync(tprof_f, 0, (size_t)D * 64, c->stream));
-  }
+  if (c->tree_prof && alloc_stamps(c, "tprof3", D, 8, &tprof_f)) return -1;
   // the whole weave in one kernel when every phase fits: k_tree_l's
   // 2,048-rank tiles and the fused tour (option fused)
   const uint32_t fr_lds = front_lds_bytes(t.nmax, FRONT_FUSED_SG);
@@ -5492,11 +5546,11 @@ int front_fused(const ListWeave &w, Front *f) {
                          (1u << bt->site_bits) - 1u);
     };
     if (tprof_f) {  // (the default front-end depth, so the clocks are the product's)
-      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, true, 4, 1>, f->sval);
-      else launch(k_weave_doc<1024, 2048, uint16_t, true, 4, 1>, sval16);
+      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, true>, f->sval);
+      else launch(k_weave_doc<1024, 2048, uint16_t, true>, sval16);
     } else {
-      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, false, 4, 1>, f->sval);
-      else launch(k_weave_doc<1024, 2048, uint16_t, false, 4, 1>, sval16);
+      if (wy) launch(k_weave_doc<1024, 2048, uint32_t, false>, f->sval);
+      else launch(k_weave_doc<1024, 2048, uint16_t, false>, sval16);
     }
   } else {
     Launch L(c, "front", (double)N * (8 + 8 + 1 + 2 + 4 + 1 + 2 + 4 + (f->skey ? 16 : 0)) + (double)N * 8);

@@ -830,11 +830,7 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
     if (!so || !sk || !sc || !sp || !st || !sa) return fail(c, "out of device memory (map outputs)");
   }
   unsigned long long *tprof = nullptr;
-  if (c->tree_prof) {
-    tprof = scratch_t<unsigned long long>(c, "mp_tprof", (size_t)P * 8);
-    if (!tprof) return fail(c, "out of device memory (tprof)");
-    HIPCHK(c, hipMemsetAsync(tprof, 0, (size_t)P * 64, c->stream));
-  }
+  if (c->tree_prof && alloc_stamps(c, "mp_tprof", P, 8, &tprof)) return -1;
   // a new epoch per call; the words are cleared only when the epoch wraps or
   // the buffer was (re)allocated for more packs than it held
   if (++pc.epoch >= 0xFFFF || lb != pc.lb || P > pc.lb_packs) {
@@ -871,11 +867,8 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
   const uint64_t S = c->pin_small[0];
   if (c->pin_small[1]) return fail(c, "cap_segs too small: %llu key weaves", (unsigned long long)S);
   if (tprof) {
-    std::vector<unsigned long long> h((size_t)P * 8);
-    HIPCHK(c, hipMemcpy(h.data(), tprof, (size_t)P * 64, hipMemcpyDeviceToHost));
-    double a[8] = {0};
-    for (uint32_t q = 0; q < P; q++)
-      for (int ph = 0; ph < 8; ph++) a[ph] += (double)h[(size_t)q * 8 + ph];
+    double a[8];
+    if (read_stamps(c, tprof, P, 8, 8, a)) return -1;
     fprintf(stderr, "map pack phases (memtime ticks per pack): sort1 %.0f keys %.0f sort2 %.0f "
             "weave+active %.0f (of which eff+sizes %.0f, siblings-before %.0f) lookback %.0f "
             "outputs %.0f\n", a[0] / P, a[1] / P, a[2] / P, (a[4] + a[6] + a[7]) / P, a[6] / P, a[7] / P,

@@ -91,6 +91,39 @@ def test_options_change_the_path_of_a_cached_layout(batch):
             assert ran <= stats and not (not_ran & stats), (options, sorted(stats))
 
 
+PHASE_LINES = ("weave phases", "front phases", "tree phases", "tour phases")
+
+
+def test_phase_stamps_do_not_change_the_weave(batch, capfd):
+    """tree_prof = 1 on every path that stamps phases: the weave is the oracle's
+    and each kernel that ran reports its phases once on stderr.  Documents of
+    3,001 nodes: two of k_tree_l's 2,048-rank tiles, three of k_tree's.  (tour
+    = 0 leaves the front end as it is, so k_front reports next to the tree.)"""
+    from tests.test_gpu_maps import check as check_maps
+
+    inputs, ref = batch
+    assert int(np.diff(inputs[0]).max()) > 2048
+    cases = [({"tree_prof": 1}, {"weave phases"}),
+             ({"tree_prof": 1, "fused": 0}, {"front phases", "tree phases", "tour phases"}),
+             ({"tree_prof": 1, "tour": 0}, {"front phases", "tree phases"}),
+             ({"tree_prof": 1, "tree_l": 0, "fused": 0}, {"front phases", "tree phases", "tour phases"})]
+    for options, lines in cases:
+        with abi.Weaver(0, options=options) as w:
+            capfd.readouterr()
+            _weave_equals_oracle(w, inputs, ref)
+        err = capfd.readouterr().err
+        assert {ln for ln in PHASE_LINES if ln in err} == lines, (options, err)
+        assert all(err.count(ln) == 1 for ln in lines), (options, err)
+
+    spec = gen.MapSpec(nodes_per_coll=60, seed=13)
+    off, idk, ck, ci, kd = gen.generate_maps(spec, 0, 40, nthreads=1)
+    with abi.Weaver(0, options={"tree_prof": 1}) as w:
+        capfd.readouterr()
+        check_maps(w, off, idk, ck, ci, kd, spec.layout()[1])
+    err = capfd.readouterr().err
+    assert err.count("map pack phases") == 1, err
+
+
 def _walk_with_4_entry_slots(w, one_doc):
     """giant_log2cap = 0 is clamped to 2 (4-entry walk slots): the giant path's
     splitter blocks of 8 nodes then overflow their slots."""
