@@ -90,6 +90,16 @@ class CwMergeResult(C.Structure):
                 ("weave", CwListResult)]
 
 
+class CwMapMergeBatch(C.Structure):
+    _fields_ = [("a", CwMapBatch), ("a_value", C.c_void_p), ("b", CwMapBatch),
+                ("b_value", C.c_void_p)]
+
+
+class CwMapMergeResult(C.Structure):
+    _fields_ = [("merged_offsets", C.POINTER(C.c_uint64)), ("merged_src", C.c_void_p),
+                ("maps", CwMapResult)]
+
+
 class CwWeftBatch(C.Structure):
     _fields_ = [("nodes", CwListBatch), ("cut", C.POINTER(C.c_uint64))]
 
@@ -204,6 +214,9 @@ def lib():
         L.cw_merge_lists.argtypes = [C.c_void_p, C.POINTER(CwMergeBatch),
                                      C.POINTER(CwMergeResult), C.c_int]
         L.cw_merge_lists.restype = C.c_int
+        L.cw_merge_maps.argtypes = [C.c_void_p, C.POINTER(CwMapMergeBatch),
+                                    C.POINTER(CwMapMergeResult), C.c_int]
+        L.cw_merge_maps.restype = C.c_int
         L.cw_weft_lists.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch), C.POINTER(CwWeftResult),
                                     C.c_int]
         L.cw_weft_lists.restype = C.c_int
@@ -274,6 +287,14 @@ class MapResult:
 
     def key_weave(self, s):
         return self.seg_perm[int(self.seg_offsets[s]):int(self.seg_offsets[s + 1])]
+
+
+@dataclass
+class MapMergeResult:
+    """Union of two node bags per collection and its map weave (cw_merge_maps)."""
+    offsets: np.ndarray      # uint64[D+1] merged collections
+    src: np.ndarray          # uint32[M] merged nodes in id order: < na_d -> a, else b (- na_d)
+    maps: MapResult          # every index is collection-local into src
 
 
 def _ptr(a):
@@ -662,3 +683,75 @@ class Weaver:
         S = int(r.n_segs)
         return MapResult(out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S],
                          out.seg_active[:S], out.seg_perm[:N + S], out.status[:D])
+
+    @staticmethod
+    def _map_batch(off, ptrs, key_bits, token_bits):
+        b = CwMapBatch()
+        b.n_colls = len(off) - 1
+        b.coll_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
+        b.id_key, b.cause, b.cause_is_id, b.kind = ptrs
+        b.key_bits = key_bits
+        b.token_bits = token_bits
+        return b
+
+    def merge_maps_device(self, a_offsets, a_ptrs, b_offsets, b_ptrs, token_bits, key_bits,
+                          src_ptr, out_ptrs, cap_segs):
+        """Device-memory call of cw_merge_maps.  a_ptrs / b_ptrs = (id_key, cause,
+        cause_is_id, kind, value) device pointers; src_ptr: merged_src (uint32
+        [Na+Nb]); out_ptrs as weave_maps_device (seg_perm sized Na+Nb+cap_segs).
+        Returns (merged offsets uint64[D+1], n_segs)."""
+        ao = np.ascontiguousarray(a_offsets, np.uint64)
+        bo = np.ascontiguousarray(b_offsets, np.uint64)
+        if len(ao) != len(bo):
+            raise ValueError("a and b must have the same number of collections")
+        vp = lambda p: C.c_void_p(p) if p else None
+        ba = self._map_batch(ao, [vp(p) for p in a_ptrs[:4]], key_bits, token_bits)
+        bb = self._map_batch(bo, [vp(p) for p in b_ptrs[:4]], key_bits, token_bits)
+        mb = CwMapMergeBatch(ba, vp(a_ptrs[4]), bb, vp(b_ptrs[4]))
+        mo = np.zeros(len(ao), np.uint64)
+        g = lambda n: C.c_void_p(out_ptrs[n])
+        r = CwMapMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
+                             CwMapResult(cap_segs, 0, g("seg_offsets"), g("seg_coll"),
+                                         g("seg_key"), g("seg_active"), g("seg_perm"),
+                                         g("status")))
+        self._check(self._L.cw_merge_maps(self._h, C.byref(mb), C.byref(r), CW_MEM_DEVICE),
+                    "cw_merge_maps")
+        return mo, int(r.maps.n_segs)
+
+    def merge_maps(self, a, b, token_bits, key_bits=0) -> MapMergeResult:
+        """Host-memory call of cw_merge_maps.  a, b: (offsets, id_key, cause,
+        cause_is_id, kind, value_token) per side, with the same number of
+        collections."""
+        def side(t):
+            off, i, c, ci, k, v = t
+            off = np.ascontiguousarray(off, np.uint64)
+            arrs = (np.ascontiguousarray(i, np.uint64), np.ascontiguousarray(c, np.uint64),
+                    np.ascontiguousarray(ci, np.uint8), np.ascontiguousarray(k, np.uint8),
+                    np.ascontiguousarray(v, np.uint64))
+            if int(off[-1]) != len(arrs[0]) or len({len(x) for x in arrs}) != 1:
+                raise ValueError("offsets[-1] != number of nodes")
+            return off, arrs
+        ao, aa = side(a)
+        bo, ab = side(b)
+        if len(ao) != len(bo):
+            raise ValueError("a and b must have the same number of collections")
+        D, NC = len(ao) - 1, len(aa[0]) + len(ab[0])
+        ba = self._map_batch(ao, [_ptr(x) for x in aa[:4]], key_bits, token_bits)
+        bb = self._map_batch(bo, [_ptr(x) for x in ab[:4]], key_bits, token_bits)
+        mb = CwMapMergeBatch(ba, _ptr(aa[4]), bb, _ptr(ab[4]))
+        mo = np.zeros(D + 1, np.uint64)
+        src = np.zeros(max(NC, 1), np.uint32)
+        cap = max(NC, 1)
+        out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
+                        np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
+                        np.zeros(NC + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
+        r = CwMapMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
+                             CwMapResult(cap, 0, _ptr(out.seg_offsets), _ptr(out.seg_coll),
+                                         _ptr(out.seg_key), _ptr(out.seg_active),
+                                         _ptr(out.seg_perm), _ptr(out.status)))
+        self._check(self._L.cw_merge_maps(self._h, C.byref(mb), C.byref(r), CW_MEM_HOST),
+                    "cw_merge_maps")
+        S, M = int(r.maps.n_segs), int(mo[-1])
+        return MapMergeResult(mo, src[:M], MapResult(
+            out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
+            out.seg_perm[:M + S], out.status[:D]))

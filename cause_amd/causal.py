@@ -9,6 +9,7 @@ order equals the full reweave).  There is no CPU weave in this module.
 
     shared.cljc:151-192   insert / append           -> insert, append, insert_bulk
     shared.cljc:300-314   merge-trees               -> merge_trees / merge_lists (cw_merge_lists)
+    map.cljc:248-249      causal-merge              -> merge_trees / merge_maps (cw_merge_maps)
     shared.cljc:268-293   weft                      -> weft / weft_lists (cw_weft_lists)
     shared.cljc:259-266   refresh-caches            -> refresh_caches
     list.cljc:20-34       weave (all arities)       -> list_weave / weave_lists
@@ -260,7 +261,12 @@ def merge_lists(pairs):
 
 
 def merge_trees(weave_fn, ct1, ct2):
-    """shared.cljc:300-314 (lists; the weave-fn is the GPU weave)."""
+    """shared.cljc:300-314; the weave-fn is the GPU weave of ct1's type (a list
+    merges through cw_merge_lists, a map through cw_merge_maps)."""
+    if ct1["type"] != ct2["type"]:
+        raise CauseError("Causal type missmatch. Merge not allowed.", {"type-missmatch"})
+    if ct1["type"] == "map":
+        return merge_maps([(ct1, ct2)])[0]
     return merge_lists([(ct1, ct2)])[0]
 
 
@@ -389,9 +395,7 @@ def weave_maps(cts):
     res = weaver().weave_maps(pm.offsets, pm.id_key, pm.cause, pm.cause_is_id, pm.kind,
                               pm.token_bits, pm.layout.key_bits)
     out = []
-    segs_of = {}
-    for s, d in enumerate(res.seg_coll.tolist()):
-        segs_of.setdefault(d, []).append(s)
+    segs_of = _segs_by_coll(res)
     for d, (ct, nodes) in enumerate(zip(cts, docs)):
         st = int(res.status[d])
         # non-Lamport causes and causes that are not nodes are the literal
@@ -399,26 +403,101 @@ def weave_maps(cts):
         # out of range or an internal check are not a ::nodes map it weaves
         if st & (abi.STATUS_DUP | abi.STATUS_MAP_KEY | abi.STATUS_INTERNAL):
             raise CauseError(f"map outside the weave's domain (status {st})", {"weave-domain"})
-        weave, active = {}, {}
-        for s in segs_of.get(d, []):
-            k = int(res.seg_key[s])
-            if k == pack.NIL:
-                key = None
-            elif k >> 63:
-                key = _unpack_id(k & ((1 << 63) - 1), pm.layout, pm.ranks[d])
-            else:
-                key = pm.keys[k]
-            # nodes are woven as [id cause-in-weave v] (map.cljc:35-41)
-            weave[key] = [ROOT_NODE] + [
-                (nodes[p][0], nodes[p][1] if pack.valid_id(nodes[p][1]) else ROOT_ID, nodes[p][2])
-                for p in res.key_weave(s)[1:]]
-            a = int(res.seg_active[s])
-            active[key] = BLANK if a < 0 else (nodes[a][0], key, nodes[a][2])
         new = dict(ct)
-        new["weave"] = weave
-        new["_active"] = active
+        new["weave"], new["_active"] = _key_weaves(res, segs_of.get(d, []), nodes, pm, d)
         out.append(new)
     return out
+
+
+def _segs_by_coll(res):
+    segs_of = {}
+    for s, d in enumerate(res.seg_coll.tolist()):
+        segs_of.setdefault(d, []).append(s)
+    return segs_of
+
+
+def _key_weaves(res, segs, nodes, pm, d):
+    """{key: key weave} and {key: active node} of collection d from the key
+    weaves `segs` of a cw_map_result, whose indices point into `nodes`."""
+    weave, active = {}, {}
+    for s in segs:
+        k = int(res.seg_key[s])
+        if k == pack.NIL:
+            key = None
+        elif k >> 63:
+            key = _unpack_id(k & ((1 << 63) - 1), pm.layout, pm.ranks[d])
+        else:
+            key = pm.keys[k]
+        # nodes are woven as [id cause-in-weave v] (map.cljc:35-41)
+        weave[key] = [ROOT_NODE] + [
+            (nodes[p][0], nodes[p][1] if pack.valid_id(nodes[p][1]) else ROOT_ID, nodes[p][2])
+            for p in res.key_weave(s)[1:]]
+        a = int(res.seg_active[s])
+        active[key] = BLANK if a < 0 else (nodes[a][0], key, nodes[a][2])
+    return weave, active
+
+
+def merge_maps(pairs):
+    """CausalMap's causal-merge (map.cljc:248-249: s/merge-trees, shared.cljc:
+    300-314, with the map weave) for many (ct1, ct2) map pairs in ONE GPU call
+    (cw_merge_maps): the union of the two ::nodes maps, deduplicated, then the
+    full map reweave.  Same checks and ex-info causes as the reference; see
+    include/causeweave.h for where the reference's own result depends on its
+    hash-map insertion order."""
+    for ct1, ct2 in pairs:
+        if ct1["type"] != ct2["type"]:
+            raise CauseError("Causal type missmatch. Merge not allowed.", {"type-missmatch"})
+        if ct1["uuid"] != ct2["uuid"]:
+            raise CauseError("Causal UUID missmatch. Merge not allowed.", {"uuid-missmatch"})
+    da = [[(i, b[0], b[1]) for i, b in ct1["nodes"].items()] for ct1, _ in pairs]
+    db = [[(i, b[0], b[1]) for i, b in ct2["nodes"].items()] for _, ct2 in pairs]
+    # one site ranking and one key-token table per pair
+    pm = pack.pack_maps([a + b for a, b in zip(da, db)])
+    tok = _Tokens()
+    vals = np.array([tok(n[2]) for d in pm.docs for n in d], np.uint64)
+    ia, ib = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    for d, (a, b) in enumerate(zip(da, db)):
+        lo = int(pm.offsets[d])
+        ia.append(np.arange(lo, lo + len(a)))
+        ib.append(np.arange(lo + len(a), lo + len(a) + len(b)))
+    ia, ib = np.concatenate(ia), np.concatenate(ib)
+    off_a = np.zeros(len(pairs) + 1, np.uint64)
+    off_a[1:] = np.cumsum([len(a) for a in da])
+    off_b = np.zeros(len(pairs) + 1, np.uint64)
+    off_b[1:] = np.cumsum([len(b) for b in db])
+    side = lambda idx, off: (off, pm.id_key[idx], pm.cause[idx], pm.cause_is_id[idx], pm.kind[idx],
+                             vals[idx])
+    res = weaver().merge_maps(side(ia, off_a), side(ib, off_b), pm.token_bits, pm.layout.key_bits)
+    segs_of = _segs_by_coll(res.maps)
+    out = []
+    for d, ((ct1, ct2), a, b) in enumerate(zip(pairs, da, db)):
+        st = int(res.maps.status[d])
+        if st & abi.STATUS_DUP:
+            raise CauseError("This node is already in the tree and can't be changed.",
+                             {"append-only", "edits-not-allowed"})
+        if st & abi.STATUS_ORPHAN:
+            raise CauseError("The cause of this node is not in the tree.", {"cause-must-exist"})
+        if st & (abi.STATUS_MAP_KEY | abi.STATUS_INTERNAL):
+            raise CauseError(f"map outside the weave's domain (status {st})", {"weave-domain"})
+        lo, hi = int(res.offsets[d]), int(res.offsets[d + 1])
+        src = res.src[lo:hi]
+        merged = [a[s] if s < len(a) else b[s - len(a)] for s in src.tolist()]
+        new = dict(ct1)
+        new["nodes"] = {n[0]: (n[1], n[2]) for n in merged}
+        new["weave"], new["_active"] = _key_weaves(res.maps, segs_of.get(d, []), merged, pm, d)
+        # insert fast-forwards ::lamport-ts to every newly inserted node (shared.cljc:179-181)
+        fresh = [merged[i][0][0] for i, s in enumerate(src.tolist()) if s >= len(a)]
+        new["lamport_ts"] = max([ct1["lamport_ts"]] + fresh)
+        out.append(new)
+    return out
+
+
+def map_insert_bulk(ct, nodes):
+    """Many s/insert calls (shared.cljc:151-184) into a map ct, as one GPU merge
+    of ``nodes`` into ``ct`` (the twin of insert_bulk)."""
+    ct2 = dict(ct)
+    ct2["nodes"] = {n[0]: (n[1], n[2]) for n in nodes}
+    return merge_trees(map_weave, ct, ct2)
 
 
 def map_weave(ct, node=None, more=None):

@@ -4446,6 +4446,15 @@ struct cw_ctx {
     bool same = false;             // this call's coll_offsets equal off (set by cw_weave_maps)
     bool verify = false;           // ... taken on trust: compared while the kernel runs
   } mpack;
+  uint32_t map_merge_fused = 1;    // map_merge_fused: one-kernel union stage of cw_merge_maps
+  struct MapMerge {                // k_map_union's pack table, cached by the two layouts
+    std::vector<uint64_t> ao, bo;
+    std::vector<uint32_t> doc0;
+    uint32_t pk = 0, dmax = 1;
+    uint32_t epoch = 0, lb_packs = 0;  // its own look-back words' epoch (mapmerge.hip)
+    const void *lb = nullptr;
+    bool ok = false;
+  } mmerge;
 };
 
 namespace {
@@ -5912,6 +5921,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 
 #include "exact.hip"
 #include "mappack.hip"
+#include "mapmerge.hip"
 #include "dist.hip"
 
 namespace {
@@ -7014,6 +7024,135 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   return 0;
 }
 
+// cw_merge_maps: uploads (host memspace), the union stage (mapmerge.hip), one
+// device-to-host copy of the merged offsets, weave_maps_impl in device memspace
+// on the merged arrays, copies out.  The merged arrays have scratch names of
+// their own (mm_*): weave_maps_impl reuses skA / svA / m_* and the sort's.
+int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result *res, int memspace) {
+  if (!bt || !res) return fail(c, "null batch/result");
+  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  const bool dev = memspace == CW_MEM_DEVICE;
+  const uint64_t D = bt->a.n_colls;
+  if (bt->b.n_colls != D) return fail(c, "a and b must have the same number of collections");
+  const uint64_t *ao = bt->a.coll_offsets, *bo = bt->b.coll_offsets;
+  if (!ao || !bo) return fail(c, "coll_offsets is required (host memory)");
+  if (ao[0] != 0 || bo[0] != 0) return fail(c, "coll_offsets[0] must be 0");
+  for (uint64_t d = 0; d < D; d++)
+    if (ao[d + 1] < ao[d] || bo[d + 1] < bo[d]) return fail(c, "coll_offsets not monotone");
+  const uint64_t Na = ao[D], Nb = bo[D], NC = Na + Nb;
+  if (NC >= 0x7FFFFFFFull) return fail(c, "merge too large: %llu nodes (limit 2^31-1)", (unsigned long long)NC);
+  for (uint64_t d = 0; d < D; d++)
+    if ((ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]) >= LINK_IDX - 1)
+      return fail(c, "collection %llu too large", (unsigned long long)d);
+  cw_map_result &M = res->maps;
+  if (!res->merged_offsets || !res->merged_src || !M.seg_offsets || !M.seg_coll || !M.seg_key ||
+      !M.seg_active || !M.seg_perm || !M.status)
+    return fail(c, "merged_offsets, merged_src and every cw_map_result array are required");
+  if (bt->a.token_bits == 0 || bt->a.token_bits > 62) return fail(c, "token_bits must be 1..62");
+  if ((Na && (!bt->a.id_key || !bt->a.cause || !bt->a.cause_is_id || !bt->a.kind || !bt->a_value)) ||
+      (Nb && (!bt->b.id_key || !bt->b.cause || !bt->b.cause_is_id || !bt->b.kind || !bt->b_value)))
+    return fail(c, "null input arrays");
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t cap = M.cap_segs;
+  uint64_t *mo = res->merged_offsets;
+  MuHost h{};
+  h.D = D;
+  h.Na = Na;
+  h.Nb = Nb;
+  h.ao = ao;
+  h.bo = bo;
+  h.key_bits = bt->a.key_bits;
+  h.a = MuSide{bt->a.id_key, bt->a.cause, bt->a_value, bt->a.cause_is_id, bt->a.kind, nullptr, nullptr};
+  h.b = MuSide{bt->b.id_key, bt->b.cause, bt->b_value, bt->b.cause_is_id, bt->b.kind, nullptr, nullptr};
+  if (!dev && NC) {  // uploads
+    uint64_t *ai = scratch_t<uint64_t>(c, "mm_aid", Na), *ac = scratch_t<uint64_t>(c, "mm_aca", Na),
+             *av = scratch_t<uint64_t>(c, "mm_ava", Na);
+    uint64_t *bi = scratch_t<uint64_t>(c, "mm_bid", Nb), *bc = scratch_t<uint64_t>(c, "mm_bca", Nb),
+             *bv = scratch_t<uint64_t>(c, "mm_bva", Nb);
+    uint8_t *as = scratch_t<uint8_t>(c, "mm_acis", Na), *ak = scratch_t<uint8_t>(c, "mm_akd", Na),
+            *bs = scratch_t<uint8_t>(c, "mm_bcis", Nb), *bk = scratch_t<uint8_t>(c, "mm_bkd", Nb);
+    if (!ai || !ac || !av || !bi || !bc || !bv || !as || !ak || !bs || !bk)
+      return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (Na) {
+      HIPCHK(c, hipMemcpy(ai, bt->a.id_key, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(ac, bt->a.cause, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(av, bt->a_value, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(as, bt->a.cause_is_id, Na, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(ak, bt->a.kind, Na, hipMemcpyHostToDevice));
+    }
+    if (Nb) {
+      HIPCHK(c, hipMemcpy(bi, bt->b.id_key, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bc, bt->b.cause, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bv, bt->b_value, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bs, bt->b.cause_is_id, Nb, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bk, bt->b.kind, Nb, hipMemcpyHostToDevice));
+    }
+    h.a = MuSide{ai, ac, av, as, ak, nullptr, nullptr};
+    h.b = MuSide{bi, bc, bv, bs, bk, nullptr, nullptr};
+  }
+  // the merged collections (device) and the union status
+  uint64_t *mid = scratch_t<uint64_t>(c, "mm_id", NC), *mca = scratch_t<uint64_t>(c, "mm_cause", NC);
+  uint8_t *mcis = scratch_t<uint8_t>(c, "mm_cis", NC), *mkd = scratch_t<uint8_t>(c, "mm_kind", NC);
+  uint32_t *msrc = dev ? res->merged_src : scratch_t<uint32_t>(c, "mm_src", NC);
+  uint32_t *ust = scratch_t<uint32_t>(c, "mm_ust", D);
+  if (!mid || !mca || !mcis || !mkd || !msrc || !ust)
+    return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
+  h.out = MuOut{mid, mca, mcis, mkd, msrc, nullptr, ust};
+  if (NC == 0) {
+    for (uint64_t d = 0; d <= D; d++) mo[d] = 0;
+  } else {
+    int rc = 1;
+    if (c->map_merge_fused) rc = map_union_fused(c, h, mo);
+    if (rc == 1) rc = map_union_general(c, h, mo);  // one oversize collection: the whole call
+    if (rc) return -1;
+  }
+  const uint64_t NM = mo[D];
+  // the map reweave of the merged collections, in device memory
+  cw_map_batch mb{};
+  mb.n_colls = D;
+  mb.coll_offsets = mo;
+  mb.id_key = mid;
+  mb.cause = mca;
+  mb.cause_is_id = mcis;
+  mb.kind = mkd;
+  mb.key_bits = bt->a.key_bits;
+  mb.token_bits = bt->a.token_bits;
+  cw_map_result mr = M;
+  if (!dev) {
+    mr.seg_offsets = scratch_t<uint64_t>(c, "mm_so", cap + 1);
+    mr.seg_coll = scratch_t<uint32_t>(c, "mm_sc", cap);
+    mr.seg_key = scratch_t<uint64_t>(c, "mm_sk", cap);
+    mr.seg_active = scratch_t<int64_t>(c, "mm_sa", cap);
+    mr.seg_perm = scratch_t<uint32_t>(c, "mm_sp", NM + cap);
+    mr.status = scratch_t<uint32_t>(c, "mm_st", D);
+    if (!mr.seg_offsets || !mr.seg_coll || !mr.seg_key || !mr.seg_active || !mr.seg_perm || !mr.status)
+      return fail(c, "out of device memory (map merge outputs)");
+  }
+  if (weave_maps_impl(c, &mb, &mr, CW_MEM_DEVICE)) return -1;
+  M.n_segs = mr.n_segs;
+  if (NC && D) {  // the union's DUP / ORPHAN join the weave's bits
+    hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, ust,
+                       mr.status, (uint32_t)D);
+    if (check_launch(c, "or_status")) return -1;
+  }
+  if (!dev) {
+    const uint64_t S = mr.n_segs;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(res->merged_src, msrc, NM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_perm, mr.seg_perm, (NM + S) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_offsets, mr.seg_offsets, (S + 1) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_coll, mr.seg_coll, S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_key, mr.seg_key, S * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_active, mr.seg_active, S * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.status, mr.status, D * 4, hipMemcpyDeviceToHost));
+  } else if (!c->async) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (c->prof) return collect_prof(c);
+  return 0;
+}
+
 int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int memspace) {
   if (!bt || !res) return fail(c, "null batch/result");
   if (memspace != CW_MEM_HOST) return fail(c, "cw_weft_lists: only CW_MEM_HOST is supported");
@@ -7206,6 +7345,7 @@ static const struct {
     {"giant_log2cap", &cw_ctx::giant_log2cap, 2, 12},
     {"map_small", &cw_ctx::map_small, 0, UINT32_MAX},
     {"map_fused", &cw_ctx::map_fused, 0, UINT32_MAX},
+    {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
     {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
 };
@@ -7299,6 +7439,12 @@ int cw_merge_lists(cw_ctx *c, const cw_merge_batch *b, cw_merge_result *r, int m
   if (!c) return -1;
   c->err.clear();
   return merge_lists_impl(c, b, r, memspace);
+}
+
+int cw_merge_maps(cw_ctx *c, const cw_map_merge_batch *b, cw_map_merge_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return merge_maps_impl(c, b, r, memspace);
 }
 
 int cw_weft_lists(cw_ctx *c, const cw_weft_batch *b, cw_weft_result *r, int memspace) {

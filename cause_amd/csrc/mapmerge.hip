@@ -1,0 +1,491 @@
+// mapmerge.hip -- the union stage of cw_merge_maps (CausalMap causal-merge,
+// map.cljc:248-249 = s/merge-trees, shared.cljc:300-314, with the map weave).
+// Included by causeweave.hip after mappack.hip (mp_sort, the look-back words)
+// and the list merge's kernels (k_merge_dedup), which the general route reuses.
+//
+// Per collection the two replicas' node bags are united by id: a repeated id
+// with the same body (cause, cause_is_id, kind, value token) is kept once (a's
+// copy), with another body it sets CW_STATUS_DUP; an id cause that names no
+// node of the union sets CW_STATUS_ORPHAN.  The merged nodes come out per
+// collection in id order (merged_src says where each came from) and go to
+// weave_maps_impl as an ordinary map batch.
+//
+// Fused route (every collection has na + nb <= MPK): k_map_union, one
+// workgroup per pack of whole consecutive collections (<= PK input nodes, <=
+// MU_MAXCOLL collections), in LDS:
+//   1. both replicas' nodes of the pack into registers (wave-blocked), a's
+//      first; bodies to LDS by pack-local index;
+//   2. a stable radix sort by (collection in pack, id) carrying the pack-local
+//      index: stability puts a's copy of a repeated id first;
+//   3. keep = the id differs from its predecessor's; a repeat compares bodies
+//      with its predecessor (DUP); a kept id-caused node binary-searches its
+//      collection's sorted ids (ORPHAN);
+//   4. a block scan of the keep flags: merged positions and per-collection
+//      merged starts;
+//   5. the pack's first merged node by a decoupled look-back over the packs
+//      (epoch-tagged words as k_map_pack's, own buffer and epoch);
+//   6. merged id / cause / cause_is_id / kind / source, the merged offsets
+//      (device u64[D+1]) and the union status at their final places.
+// LDS at PK = 2048: sorted keys, causes, values 3 x 16 KiB, sort values /
+// merged positions 4 KiB, kind bytes 2 KiB, sort counters 2.3 KiB, plus 8 B a
+// collection of the fullest pack (<= 4 KiB): under 64 KiB.  PK = 512: 19 KiB.
+//
+// General route (a larger collection, sort keys over 63 bits, or
+// map_merge_fused = 0): the list merge's scheme -- a then b per collection into
+// capacity slots, the segmented radix sort by id, k_merge_dedup's count pass,
+// host offsets, its write pass -- with cause_is_id riding in bits 6-7 of the
+// kind byte, then k_mm_finish per collection (unpack, orphan search).
+
+constexpr uint32_t MU_MAXCOLL = 512;  // most collections in one pack (LDS: 8 B each)
+
+// body byte: kind (low 6 bits) | cause_is_id << 6 -- both routes compare and
+// carry the same byte, so their results are identical
+__host__ __device__ __forceinline__ uint8_t mu_body8(uint8_t kind, uint8_t cis) {
+  return (uint8_t)((kind & 0x3Fu) | ((cis & 3u) << 6));
+}
+
+struct MuSide {
+  const uint64_t *id, *cause, *val;
+  const uint8_t *cis, *kind;
+  const uint64_t *off;    // device [D+1]
+  const uint64_t *pack0;  // device [P+1]: each pack's first node of this side
+};
+
+struct MuOut {
+  uint64_t *id, *cause;
+  uint8_t *cis, *kind;
+  uint32_t *src;
+  uint64_t *off;     // device [D+1] merged offsets
+  uint32_t *status;  // [D] union status
+};
+
+template <int PK, int NT>
+__global__ __launch_bounds__(NT) void k_map_union(MuSide sa, MuSide sb,
+                                                  const uint32_t *__restrict__ pack_doc0, uint32_t P,
+                                                  uint32_t D, unsigned long long *lb, uint32_t epoch,
+                                                  uint32_t nd_max, MuOut out, uint32_t *ctl) {
+  constexpr uint32_t IT = PK / NT;
+  __shared__ uint64_t A[PK], C[PK], V[PK];
+  __shared__ uint16_t VS[PK];
+  __shared__ uint8_t K8[PK];
+  extern __shared__ uint32_t mu_dyn[];  // dstat[nd_max], astart[nd_max + 1], bstart[nd_max + 1]
+  uint32_t *const dstat = mu_dyn;
+  uint16_t *const astart = reinterpret_cast<uint16_t *>(mu_dyn + nd_max);
+  uint16_t *const bstart = astart + (nd_max + 1);
+  __shared__ uint32_t wcnt[NT / 64][SUB_BINS], run[64], wtot[NT / 64];
+  __shared__ uint32_t s_base;
+  __shared__ unsigned long long s_or;
+
+  const uint32_t pk = blockIdx.x, tid = threadIdx.x;
+  const uint32_t d0 = pack_doc0[pk], nd = pack_doc0[pk + 1] - d0;
+  const uint64_t a0 = sa.pack0[pk], b0 = sb.pack0[pk];
+  const uint32_t la = (uint32_t)(sa.pack0[pk + 1] - a0), len = la + (uint32_t)(sb.pack0[pk + 1] - b0);
+  // 1. the pack's nodes, a's then b's: the loads go out first
+  uint64_t lid[IT], lc[IT], lv[IT];
+  uint8_t lk[IT];
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    const uint32_t j = wb_elem<IT>(u);
+    const bool ok = j < len, fa = j < la;
+    const uint64_t g = fa ? a0 + j : b0 + (j - la);
+    const uint64_t *pi = fa ? sa.id : sb.id, *pc = fa ? sa.cause : sb.cause, *pv = fa ? sa.val : sb.val;
+    const uint8_t *pk8 = fa ? sa.kind : sb.kind, *ps = fa ? sa.cis : sb.cis;
+    lid[u] = ok ? pi[g] : 0ull;
+    lc[u] = ok ? pc[g] : 0ull;
+    lv[u] = ok ? pv[g] : 0ull;
+    lk[u] = ok ? mu_body8(pk8[g], ps[g]) : (uint8_t)0;
+  }
+  for (uint32_t i = tid; i <= nd; i += NT) {
+    astart[i] = (uint16_t)(sa.off[d0 + i] - a0);
+    bstart[i] = (uint16_t)(sb.off[d0 + i] - b0);
+  }
+  for (uint32_t i = tid; i < nd; i += NT) dstat[i] = 0;
+  if (tid == 0) s_or = 0;
+  __syncthreads();
+
+  uint64_t ck[IT];
+  uint32_t val[IT], dl0[IT];
+  unsigned long long oid = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    const uint32_t j = wb_elem<IT>(u);
+    ck[u] = 0;
+    val[u] = 0;
+    dl0[u] = 0;
+    if (j < len) {
+      const bool fa = j < la;
+      const uint16_t *st = fa ? astart : bstart;
+      const uint32_t jj = fa ? j : j - la;
+      uint32_t lo = 0, hi = nd;  // the collection of element j
+      while (hi - lo > 1) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (st[m] <= jj) lo = m; else hi = m;
+      }
+      C[j] = lc[u];
+      V[j] = lv[u];
+      K8[j] = lk[u];
+      ck[u] = lid[u];
+      oid |= lid[u];
+      val[u] = j;
+      dl0[u] = lo;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) oid |= __shfl_xor(oid, o, 64);
+  if ((tid & 63) == 0 && oid) atomicOr(&s_or, oid);
+  __syncthreads();
+  // 2. stable sort by (collection, id); the key widths are this pack's own
+  const uint32_t kbits = s_or ? 64 - __builtin_clzll(s_or) : 1;
+  const uint32_t dbits = nd > 1 ? 32 - __builtin_clz(nd - 1) : 0;
+  const bool fits = kbits + dbits <= 63;  // otherwise the general route (host)
+  if (!fits && tid == 0) atomicOr(&ctl[0], 1u);
+  const uint32_t ksh = fits ? kbits : 63;  // (keys are 0 then: collection 0)
+  const uint64_t imask = (1ull << min(kbits, 63u)) - 1;
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) ck[u] = fits ? (((uint64_t)dl0[u] << kbits) | ck[u]) : 0ull;
+  mp_sort<NT, IT>(ck, val, len, fits ? kbits + dbits : 1, A, VS, wcnt, run);
+
+  // 3. keep flags, body conflicts, orphans -- item u is sorted position wb_elem(u)
+  bool keep[IT];
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    const uint32_t i = wb_elem<IT>(u);
+    keep[u] = false;
+    if (i >= len) continue;
+    const uint32_t dl = (uint32_t)(ck[u] >> ksh), j = val[u];
+    keep[u] = i == 0 || A[i - 1] != ck[u];
+    if (!keep[u]) {  // a repeated id: the same body, or edits-not-allowed
+      const uint32_t jp = VS[i - 1];
+      if (C[jp] != C[j] || V[jp] != V[j] || K8[jp] != K8[j]) atomicOr(&dstat[dl], (uint32_t)CW_STATUS_DUP);
+    } else if ((K8[j] >> 6) == 1) {  // an id cause must name a node of the union
+      const uint64_t c = C[j], want = ((uint64_t)dl << ksh) | c;
+      uint32_t lo = (uint32_t)astart[dl] + bstart[dl];
+      const uint32_t e1 = (uint32_t)astart[dl + 1] + bstart[dl + 1];
+      uint32_t hi = e1;
+      const bool inrange = (c & ~imask) == 0;
+      while (inrange && lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (A[m] < want) lo = m + 1; else hi = m;
+      }
+      if (!(inrange && lo < e1 && A[lo] == want)) atomicOr(&dstat[dl], (uint32_t)CW_STATUS_ORPHAN);
+    }
+  }
+  // 4. merged position = kept nodes before me: ballots inside a row of 64, the
+  // wave's rows in order, then the waves
+  uint32_t pos[IT], rowsum = 0;
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    const uint64_t m = __ballot(keep[u]);
+    pos[u] = rowsum + lanes_below(m);
+    rowsum += (uint32_t)__popcll(m);
+  }
+  if ((tid & 63) == 0) wtot[tid >> 6] = rowsum;
+  __syncthreads();  // (also: every VS read of step 3 is done)
+  uint32_t before = 0, tot = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < NT / 64; w++) {
+    const uint32_t t = wtot[w];
+    before += w < (tid >> 6) ? t : 0u;
+    tot += t;
+  }
+  uint16_t *const POS = VS;  // exclusive count of kept nodes at each sorted position
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    pos[u] += before;
+    if (wb_elem<IT>(u) < len) POS[wb_elem<IT>(u)] = (uint16_t)pos[u];
+  }
+  // 5. publish this pack's merged count, then sum the predecessors' (one wave)
+  const unsigned long long ep = (unsigned long long)epoch << LB_EPOCH;
+  if (tid == 0) {
+    const unsigned long long w = (pk == 0 ? LB_INC : LB_AGG) | ep | tot;
+    __hip_atomic_store(lb + pk, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (tid < 64) {
+    const uint32_t lane = tid;
+    uint32_t base = 0;
+    if (pk > 0) {
+      for (int64_t q0 = (int64_t)pk - 1;;) {
+        const int64_t q = q0 - lane;  // lane 0 = the nearest predecessor
+        unsigned long long v = q >= 0 ? __hip_atomic_load(lb + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                                      : (LB_INC | ep);
+        if (((v >> LB_EPOCH) & 0xFFFFull) != epoch) v = 0;  // an earlier call's word
+        const uint64_t inc = __ballot((v >> 62) == 2), none = __ballot((v >> 62) == 0);
+        const uint32_t first = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive
+        const uint64_t need = first >= 63 ? ~0ull : ((2ull << first) - 1);
+        if (none & need) {  // a pack in this window has not counted yet
+          __builtin_amdgcn_s_sleep(1);
+          continue;
+        }
+        uint32_t x = lane <= first ? (uint32_t)v : 0u;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+        base += x;
+        if (first < 64) break;
+        q0 -= 64;
+      }
+      if (lane == 0)
+        __hip_atomic_store(lb + pk, LB_INC | ep | (unsigned long long)(base + tot), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (lane == 0) s_base = base;
+  }
+  __syncthreads();
+  const uint32_t base = s_base;
+  // 6. outputs at their final places
+#pragma unroll
+  for (uint32_t u = 0; u < IT; u++) {
+    if (!keep[u]) continue;
+    const uint32_t dl = (uint32_t)(ck[u] >> ksh), j = val[u];
+    const uint32_t o = base + pos[u];
+    const uint8_t k8 = K8[j];
+    const uint32_t na = (uint32_t)astart[dl + 1] - astart[dl];
+    out.id[o] = ck[u] & imask;
+    out.cause[o] = C[j];
+    out.cis[o] = (uint8_t)(k8 >> 6);
+    out.kind[o] = (uint8_t)(k8 & 0x3Fu);
+    out.src[o] = j < la ? j - astart[dl] : na + (j - la - bstart[dl]);
+  }
+  for (uint32_t dl = tid; dl < nd; dl += NT) {
+    const uint32_t cs = (uint32_t)astart[dl] + bstart[dl];
+    out.off[d0 + dl] = (uint64_t)base + (cs < len ? (uint32_t)POS[cs] : tot);
+    out.status[d0 + dl] = dstat[dl];
+  }
+  if (pk == P - 1 && tid == 0) out.off[D] = (uint64_t)base + tot;
+}
+
+// General route.  Collection d's a-nodes then b-nodes into one capacity slot
+// [coff[d], coff[d+1]); the kind byte carries cause_is_id (mu_body8).
+__global__ __launch_bounds__(256) void k_mm_concat(MuSide sa, MuSide sb,
+                                                   const uint32_t *__restrict__ coff,
+                                                   uint64_t *__restrict__ cid,
+                                                   uint64_t *__restrict__ ccause,
+                                                   uint8_t *__restrict__ ckind,
+                                                   uint64_t *__restrict__ cval) {
+  const uint32_t d = blockIdx.x;
+  const uint64_t a0 = sa.off[d], b0 = sb.off[d];
+  const uint32_t na = (uint32_t)(sa.off[d + 1] - a0), nb = (uint32_t)(sb.off[d + 1] - b0);
+  const uint32_t c0 = coff[d];
+  for (uint32_t i = threadIdx.x; i < na + nb; i += blockDim.x) {
+    const bool fa = i < na;
+    const uint64_t g = fa ? a0 + i : b0 + (i - na);
+    cid[c0 + i] = fa ? sa.id[g] : sb.id[g];
+    ccause[c0 + i] = fa ? sa.cause[g] : sb.cause[g];
+    ckind[c0 + i] = fa ? mu_body8(sa.kind[g], sa.cis[g]) : mu_body8(sb.kind[g], sb.cis[g]);
+    cval[c0 + i] = fa ? sa.val[g] : sb.val[g];
+  }
+}
+
+// Merged collection d = [moff[d], moff[d+1]), ids ascending: the kind byte is
+// unpacked into kind and cause_is_id, and every id cause is searched among the
+// collection's ids (a miss: CW_STATUS_ORPHAN).
+__global__ __launch_bounds__(256) void k_mm_finish(const uint64_t *__restrict__ mid,
+                                                   const uint64_t *__restrict__ mcause,
+                                                   const uint32_t *__restrict__ moff,
+                                                   uint8_t *__restrict__ mkind,
+                                                   uint8_t *__restrict__ mcis,
+                                                   uint32_t *__restrict__ mstatus) {
+  const uint32_t d = blockIdx.x, m0 = moff[d], m1 = moff[d + 1];
+  bool orphan = false;
+  for (uint32_t i = m0 + threadIdx.x; i < m1; i += blockDim.x) {
+    const uint8_t k8 = mkind[i], cis = (uint8_t)(k8 >> 6);
+    mkind[i] = (uint8_t)(k8 & 0x3Fu);
+    mcis[i] = cis;
+    if (cis != 1) continue;
+    const uint64_t want = mcause[i];
+    uint32_t lo = m0, hi = m1;
+    while (lo < hi) {
+      const uint32_t m = (lo + hi) >> 1;
+      if (mid[m] < want) lo = m + 1; else hi = m;
+    }
+    orphan |= !(lo < m1 && mid[lo] == want);
+  }
+  if (__syncthreads_or(orphan) && threadIdx.x == 0) mstatus[d] |= CW_STATUS_ORPHAN;
+}
+
+namespace {
+
+struct MuHost {  // what merge_maps_impl hands the union stage (device pointers)
+  uint64_t D, Na, Nb;
+  const uint64_t *ao, *bo;  // host offsets
+  MuSide a, b;              // (off / pack0 filled in by the routes)
+  MuOut out;                // (off filled in by the fused route)
+  uint32_t key_bits;
+};
+
+// The fused route.  Returns 1 when it does not apply (the caller takes the
+// general route), 0 on success with the merged offsets in `mo` (host), -1 on
+// error.
+int map_union_fused(cw_ctx *c, MuHost &h, uint64_t *mo) {
+  const uint64_t D = h.D, *ao = h.ao, *bo = h.bo;
+  auto &mm = c->mmerge;
+  const bool same = mm.ao.size() == D + 1 && mm.bo.size() == D + 1 &&
+                    memcmp(mm.ao.data(), ao, (D + 1) * 8) == 0 &&
+                    memcmp(mm.bo.data(), bo, (D + 1) * 8) == 0;
+  if (!same) {  // pack table, cached while both layouts repeat
+    uint64_t mx = 0;
+    for (uint64_t d = 0; d < D; d++) mx = std::max(mx, (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]));
+    mm.ao.assign(ao, ao + D + 1);
+    mm.bo.assign(bo, bo + D + 1);
+    mm.ok = mx <= MPK;
+    mm.pk = mx <= 512 ? 512u : mx <= 1024 ? 1024u : MPK;
+    mm.doc0.clear();
+    mm.dmax = 1;
+    if (mm.ok) {
+      for (uint64_t d = 0; d < D;) {
+        const uint64_t s = d;
+        while (d < D && (ao[d + 1] - ao[s]) + (bo[d + 1] - bo[s]) <= mm.pk && d - s < MU_MAXCOLL) d++;
+        mm.doc0.push_back((uint32_t)s);
+        mm.dmax = std::max<uint32_t>(mm.dmax, (uint32_t)(d - s));
+      }
+      mm.doc0.push_back((uint32_t)D);
+      const size_t P1 = mm.doc0.size();
+      std::vector<uint64_t> pa(P1), pb(P1);
+      for (size_t k = 0; k < P1; k++) {
+        pa[k] = ao[mm.doc0[k]];
+        pb[k] = bo[mm.doc0[k]];
+      }
+      uint32_t *dp = scratch_t<uint32_t>(c, "mm_doc0", P1);
+      uint64_t *dpa = scratch_t<uint64_t>(c, "mm_pa0", P1), *dpb = scratch_t<uint64_t>(c, "mm_pb0", P1);
+      uint64_t *dao = scratch_t<uint64_t>(c, "mm_aoff", D + 1), *dbo = scratch_t<uint64_t>(c, "mm_boff", D + 1);
+      if (!dp || !dpa || !dpb || !dao || !dbo) {
+        mm.ao.clear();
+        return fail(c, "out of device memory (map merge packs)");
+      }
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipMemcpy(dp, mm.doc0.data(), P1 * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dpa, pa.data(), P1 * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dpb, pb.data(), P1 * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dao, ao, (D + 1) * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dbo, bo, (D + 1) * 8, hipMemcpyHostToDevice));
+    }
+  }
+  if (!mm.ok) return 1;
+  const uint32_t P = (uint32_t)mm.doc0.size() - 1;
+  const uint64_t NC = h.Na + h.Nb;
+  unsigned long long *lb = scratch_t<unsigned long long>(c, "mm_lb", P);
+  uint32_t *ctl = scratch_t<uint32_t>(c, "mm_ctl", 4);
+  uint64_t *dmo = scratch_t<uint64_t>(c, "mm_moff", D + 1);
+  if (!lb || !ctl || !dmo) return fail(c, "out of device memory (map merge)");
+  // a new epoch per call; the words are cleared only when the epoch wraps or
+  // the buffer was (re)allocated or holds fewer packs than this call has
+  if (++mm.epoch >= 0xFFFF || lb != mm.lb || P > mm.lb_packs) {
+    HIPCHK(c, hipMemsetAsync(lb, 0, (size_t)P * 8, c->stream));
+    mm.epoch = 1;
+    mm.lb = lb;
+    mm.lb_packs = P;
+  }
+  HIPCHK(c, hipMemsetAsync(ctl, 0, 16, c->stream));
+  h.a.off = (const uint64_t *)c->bufs["mm_aoff"].p;
+  h.b.off = (const uint64_t *)c->bufs["mm_boff"].p;
+  h.a.pack0 = (const uint64_t *)c->bufs["mm_pa0"].p;
+  h.b.pack0 = (const uint64_t *)c->bufs["mm_pb0"].p;
+  h.out.off = dmo;
+  const uint32_t *dp = (const uint32_t *)c->bufs["mm_doc0"].p;
+  const size_t dyn = (size_t)mm.dmax * 4 + (size_t)(mm.dmax + 1) * 4;
+  size_t stat_idx = (size_t)-1;
+  {
+    // 26 B per input node here; 22 B per merged node join once the count is known
+    Launch L(c, "map_union", (double)NC * 26);
+#define CW_MAP_UNION_LAUNCH(PK_, NT_)                                                            \
+  hipLaunchKernelGGL((k_map_union<PK_, NT_>), dim3(P), dim3(NT_), dyn, c->stream, h.a, h.b, dp, P, \
+                     (uint32_t)D, lb, mm.epoch, mm.dmax, h.out, ctl)
+    if (mm.pk == 512) CW_MAP_UNION_LAUNCH(512, 128);
+    else if (mm.pk == 1024) CW_MAP_UNION_LAUNCH(1024, 256);
+    else CW_MAP_UNION_LAUNCH(2048, 512);
+#undef CW_MAP_UNION_LAUNCH
+    if (L.a) stat_idx = c->pending.size();  // (its record is pushed when L goes out of scope)
+  }
+  if (check_launch(c, "map_union")) return -1;
+  // the one device-to-host copy of the stage: the merged offsets (and the flag)
+  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(mo, dmo, (D + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (c->pin_small[0]) {  // a pack's sort keys need more than 63 bits
+    if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes = 0;
+    return 1;
+  }
+  if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes += (double)mo[D] * 22;
+  return 0;
+}
+
+// The general route: the list merge's scheme with map bodies.
+int map_union_general(cw_ctx *c, MuHost &h, uint64_t *mo) {
+  const uint64_t D = h.D, *ao = h.ao, *bo = h.bo, NC = h.Na + h.Nb;
+  if (!grid_ok(D, 1024)) return fail(c, "batch too large for one dispatch");
+  std::vector<uint64_t> cap(D + 1);
+  std::vector<uint32_t> h_co(D + 1);
+  for (uint64_t d = 0; d <= D; d++) {
+    cap[d] = ao[d] + bo[d];
+    h_co[d] = (uint32_t)cap[d];
+  }
+  uint64_t *dao = scratch_t<uint64_t>(c, "mm_aoff", D + 1), *dbo = scratch_t<uint64_t>(c, "mm_boff", D + 1);
+  uint32_t *dco = scratch_t<uint32_t>(c, "mm_coff", D + 1), *dmo = scratch_t<uint32_t>(c, "mm_moff32", D + 1);
+  uint64_t *cid = scratch_t<uint64_t>(c, "mm_cid", NC), *cca = scratch_t<uint64_t>(c, "mm_cca", NC),
+           *cva = scratch_t<uint64_t>(c, "mm_cva", NC);
+  uint8_t *ckd = scratch_t<uint8_t>(c, "mm_ckd", NC);
+  uint32_t *mcnt = scratch_t<uint32_t>(c, "mm_cnt", D + 1);
+  uint64_t *skA = scratch_t<uint64_t>(c, "mm_skA", NC), *skB = scratch_t<uint64_t>(c, "mm_skB", NC);
+  uint32_t *svA = scratch_t<uint32_t>(c, "mm_svA", NC), *svB = scratch_t<uint32_t>(c, "mm_svB", NC);
+  if (!dao || !dbo || !dco || !dmo || !cid || !cca || !cva || !ckd || !mcnt || !skA || !skB || !svA || !svB)
+    return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
+  c->mmerge.ao.clear();  // (mm_aoff / mm_boff are rewritten: the fused route's cache is void)
+  c->mmerge.bo.clear();
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(dao, ao, (D + 1) * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dbo, bo, (D + 1) * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dco, h_co.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  h.a.off = dao;
+  h.b.off = dbo;
+  // 1. union: a then b per collection, in capacity slots
+  {
+    Launch L(c, "mm_concat", (double)NC * 52);
+    hipLaunchKernelGGL(k_mm_concat, dim3((uint32_t)D), dim3(256), 0, c->stream, h.a, h.b, dco, cid, cca,
+                       ckd, cva);
+  }
+  if (check_launch(c, "mm_concat")) return -1;
+  // 2. id order per capacity slot (the general segmented radix sort)
+  if (ensure_tables(c, D, cap.data())) return -1;
+  uint32_t key_bits = h.key_bits;
+  if (key_bits == 0 && find_key_bits(c, cid, (uint32_t)NC, &key_bits)) return -1;
+  uint64_t *skey;
+  uint32_t *sval;
+  if (radix_sort<uint64_t>(c, "mm_idsort", cid, nullptr, skA, svA, skB, svB, key_bits, 0, (uint32_t)NC,
+                           &skey, &sval))
+    return -1;
+  // 3. dedup: count, host offsets, write (the list merge's kernel)
+  {
+    Launch L(c, "mm_count", (double)NC * 12);
+    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval, cca,
+                       ckd, cva, dco, 0, mcnt, dmo, h.out.id, h.out.cause, h.out.kind, h.out.src,
+                       h.out.status);
+  }
+  if (check_launch(c, "mm_count")) return -1;
+  std::vector<uint32_t> h_cnt(D), h_mo(D + 1);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
+  mo[0] = 0;
+  for (uint64_t d = 0; d < D; d++) {
+    mo[d + 1] = mo[d] + h_cnt[d];
+    h_mo[d] = (uint32_t)mo[d];
+  }
+  h_mo[D] = (uint32_t)mo[D];
+  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  {
+    Launch L(c, "mm_write", (double)NC * 12 + (double)mo[D] * 21);
+    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval, cca,
+                       ckd, cva, dco, 1, mcnt, dmo, h.out.id, h.out.cause, h.out.kind, h.out.src,
+                       h.out.status);
+  }
+  if (check_launch(c, "mm_write")) return -1;
+  // 4. kind / cause_is_id apart again, and the orphan search
+  {
+    Launch L(c, "mm_finish", (double)mo[D] * 19);
+    hipLaunchKernelGGL(k_mm_finish, dim3((uint32_t)D), dim3(256), 0, c->stream, h.out.id, h.out.cause, dmo,
+                       h.out.kind, h.out.cis, h.out.status);
+  }
+  if (check_launch(c, "mm_finish")) return -1;
+  return 0;
+}
+
+}  // namespace

@@ -317,6 +317,53 @@ typedef struct {
 int cw_merge_lists(cw_ctx *ctx, const cw_merge_batch *batch, cw_merge_result *result,
                    int memspace);
 
+/* Maps: CausalMap's causal-merge (map.cljc:248-249), s/merge-trees with the
+ * map weave.  Per collection the result is the full map reweave (c.map/weave
+ * 1-arity, as cw_weave_maps) of the union of the two ::nodes bags deduplicated
+ * by id, with cw_merge_lists' conventions:
+ *   - the same id with the same body (cause, cause_is_id, kind, value token)
+ *     is kept once, a's copy;
+ *   - the same id with another body sets CW_STATUS_DUP;
+ *   - a cause with cause_is_id = 1 that names no node of the union sets
+ *     CW_STATUS_ORPHAN (shared.cljc:175-178; key causes are exempt, :175).
+ *     The root id [0 "0" 0] is no node of a map, so a node caused by it is an
+ *     orphan too.  The collection is still woven as cw_weave_maps weaves it
+ *     (the nil key); the bit is information for the caller, as NON_LAMPORT is.
+ * The union's bits are OR'ed into the weave's status.
+ * This is the reference's merge for the collections CausalBase makes, where
+ * every id cause names a key-caused node (undo / redo nodes hang under value
+ * nodes), whenever the reference does not throw (it inserts ct2's nodes in
+ * hash-map order and throws :cause-must-exist when a node precedes its cause).
+ * Where an id cause names an id-caused or absent node (id keys,
+ * the nil key) weave-node appends in arrival order, so the reference's own
+ * result depends on ct2's hash-map order; for those collections the result is
+ * what s/refresh-caches gives for the merged ::nodes.
+ * Limits: Na + Nb < 2^31 - 1; per collection cw_weave_maps' limit.  Empty
+ * collections, on one side or both, are legal (status 0, no key weaves).
+ * When every collection has na + nb <= 2048 the union is one kernel per pack
+ * of collections (mapmerge.hip); one larger collection sends the whole call
+ * through the general union (sorts and two dedup passes). */
+typedef struct {
+  cw_map_batch a;          /* replica 1 (coll_offsets: host memory)                    */
+  const uint64_t *a_value; /* [Na] value token: equal tokens <=> equal values          */
+  cw_map_batch b;          /* replica 2, same n_colls; key_bits / token_bits unused    */
+  const uint64_t *b_value; /* [Nb]                                                     */
+} cw_map_merge_batch;
+
+typedef struct {
+  uint64_t *merged_offsets; /* HOST [n_colls+1]                                        */
+  uint32_t *merged_src;     /* [Na+Nb]: merged nodes per collection in id order;
+                               s < na_d is a's collection-local s, else b's s - na_d   */
+  cw_map_result maps;       /* cw_weave_maps' result for the merged collections; every
+                               index is collection-local into merged_src; seg_perm
+                               sized Na+Nb+cap_segs                                    */
+} cw_map_merge_result;
+
+/* memspace: where the node arrays of a and b, merged_src and the arrays of
+ * `maps` live; the two coll_offsets and merged_offsets are always host memory. */
+int cw_merge_maps(cw_ctx *ctx, const cw_map_merge_batch *batch, cw_map_merge_result *result,
+                  int memspace);
+
 /* ----------------------------------------------------------------- weft ---- */
 /* s/weft (shared.cljc:268-293), time travel: per document, the root and each
  * named site's yarn up to and including its cut id, nothing of the other
