@@ -3205,11 +3205,13 @@ __global__ __launch_bounds__(256) void k_emit(
 //   walk   every sublist (splitter to splitter) for its length and successor
 //          sublist; each lane runs its own walker state machine and takes the
 //          next sublist from an LDS counter as soon as one ends (a wave never
-//          waits for its longest walk); each node's (sublist, index) goes to
-//          HBM scratch with fire-and-forget stores;
+//          waits for its longest walk); each node's sublist (u16) goes to HBM
+//          scratch with fire-and-forget stores, its index inside the sublist
+//          into its own successor slot, dead once the walker has read it;
 //   jump   suffix sums over the sublists by pointer jumping -> sublist bases
 //          (asynchronous: no barrier between the hops);
-//   place  coalesced over nodes: position = base + index, sval (u16) into an
+//   place  coalesced over nodes (their indices taken into registers first:
+//          the weave reuses the slots): position = base + index, sval (u16) into an
 //          LDS weave where the successors were, render bits by position;
 //   write  weave_perm and render bytes, coalesced.
 // Replaces k_walk + k_rank + k_emit and their slot buffer in HBM.
@@ -3231,7 +3233,7 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
                                              uint64_t *__restrict__ max_ts,
                                              uint32_t *__restrict__ perm, uint32_t *__restrict__ vbits,
                                              uint32_t *__restrict__ vcount,
-                                             uint32_t *__restrict__ status, uint32_t *loc,
+                                             uint32_t *__restrict__ status, uint16_t *loc,
                                              unsigned long long *__restrict__ tprof,
                                              uint32_t d, uint32_t *sm) {
   constexpr uint32_t SPT = 8;  // sublists per thread in the jumping rounds: S <= SPT * NT
@@ -3249,7 +3251,8 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
   const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const uint32_t base = doc_off[d], n = doc_off[d + 1] - base, log2k = doc_log2k[d];
   const uint32_t *const linkD = link + base;
-  uint32_t *const locD = loc + base, *const permD = perm + base;
+  uint16_t *const locD = loc + base;
+  uint32_t *const permD = perm + base;
   if (tid == 0 && max_ts) max_ts[d] = n ? (skey[base + n - 1] >> ts_shift) : 0ull;
   if (n == 0) return;
   const uint32_t S = (n + (1u << log2k) - 1) >> log2k, nw = (n + 31) / 32;
@@ -3291,24 +3294,40 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
   stamp(0);
   bool bad = false;
   // pass 1: per-lane walker state machines over the sublists; every node's
-  // (sublist, index inside it) goes to HBM scratch (fire-and-forget stores).
+  // sublist goes to HBM scratch as a u16 (fire-and-forget stores) and its
+  // index inside the sublist into the node's own successor slot in LDS: the
+  // walker standing on a node has read that slot already (program order in the
+  // lane), and no other walker uses it.  The one other reader of a slot is the
+  // previous sublist's walker arriving at a sublist's head: it loads succ[us]
+  // together with the splitter word and discards it, because the splitter bit
+  // ends its sublist (hence the relaxed workgroup-scope accesses: the race is
+  // on a value nobody uses).  With a corrupt link table a walker may read a
+  // slot that already holds an index: us is clamped and cnt bounded as
+  // before, and the checks below end the document INTERNAL.
   // A step reads the node's successor and its splitter bit together (one LDS
   // round trip a node; round 5: 12.28 -> 12.22 ms a config-2 step.  Two
   // walkers a lane stepped together lost, 12.54 ms, and so did the tree's two
   // chains a lane in its list walk and pointer jumping, 13.04 ms:
   // profiles/r05_tour_chains_ab.txt)
   {
+    auto slot_ld = [&](uint32_t i) -> uint32_t {
+      return __hip_atomic_load(&succ[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    auto slot_st = [&](uint32_t i, uint32_t x) {
+      __hip_atomic_store(&succ[i], (uint16_t)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
     uint32_t j = tid, u = 0, cnt = 0;
     bool live = j < S;
     if (live) {
       const uint32_t v = split_node(d, j, log2k, n);
-      lane_at(locD, v) = j << 16;
-      u = succ[v];
+      u = slot_ld(v);
+      lane_at(locD, v) = (uint16_t)j;
+      slot_st(v, 0u);
       cnt = 1;
     }
     while (live) {
       const uint32_t us = u < n ? u : 0u;
-      const uint32_t nx = succ[us], sw = sbm[us >> 5];  // both reads in flight
+      const uint32_t nx = slot_ld(us), sw = sbm[us >> 5];  // both reads in flight
       const bool end = u >= n || ((sw >> (us & 31)) & 1u) || cnt > n;
       if (end) {
         bad |= (u != TOUR_END && u >= n) || cnt > n;
@@ -3317,12 +3336,14 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
         live = j < S;
         if (live) {
           const uint32_t v = split_node(d, j, log2k, n);
-          lane_at(locD, v) = j << 16;
-          u = succ[v];
+          u = slot_ld(v);
+          lane_at(locD, v) = (uint16_t)j;
+          slot_st(v, 0u);
           cnt = 1;
         }
       } else {
-        lane_at(locD, u) = (j << 16) | cnt;
+        lane_at(locD, u) = (uint16_t)j;
+        slot_st(u, cnt);
         cnt++;
         u = nx;
       }
@@ -3402,13 +3423,33 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
   // successors and splitter bits were, then written out coalesced.  (The
   // scratch stores above are read by other waves of this workgroup: one CU,
   // one L1, lines not cached before; the barriers order them.)  The barrier
-  // below is the one that ends the ranking.
+  // below is the one that ends the ranking.  out[] takes the place of the
+  // successor slots, which hold the walk's indices: every thread takes those
+  // of its nodes r = tid + k NT into registers before that barrier, two a
+  // VGPR (n < 2^16: at most NB * LU = 64 a thread; compile-time indices only,
+  // the batches unrolled, so the array stays in registers).
   uint16_t *out = succ;
   uint32_t *pvis = sbm;
+  constexpr uint32_t NB = 0x10000u / (NT * LU);  // placement batches of a u16 document
+  static_assert(NB * NT * LU == 0x10000u && LU % 2 == 0, "the index registers cover n < 2^16");
+  uint32_t ix[NB][LU / 2];
+#pragma unroll
+  for (uint32_t b = 0; b < NB; b++) {
+    if (b * NT * LU >= n) break;
+#pragma unroll
+    for (uint32_t k = 0; k < LU; k += 2) {
+      const uint32_t r = tid + (b * LU + k) * NT;
+      const uint32_t lo = r < n ? succ[r] : 0u, hi = r + NT < n ? succ[r + NT] : 0u;
+      ix[b][k / 2] = lo | hi << 16;
+    }
+  }
   for (uint32_t w = tid; w < nw; w += NT) pvis[w] = 0;
   __syncthreads();
   if (tid == 0 && (sub[0] & 0xFFFFu) != n) bad_s = 1;  // the root's sublist starts the tour
-  for (uint32_t r0 = tid; r0 < n; r0 += NT * LU) {
+#pragma unroll
+  for (uint32_t b = 0; b < NB; b++) {
+    if (b * NT * LU >= n) break;
+    const uint32_t r0 = tid + b * NT * LU;
     uint32_t lc[LU], x[LU];
 #pragma unroll
     for (uint32_t k = 0; k < LU; k++) {
@@ -3420,8 +3461,9 @@ __device__ __forceinline__ void tour_doc(const uint32_t *__restrict__ link,
     for (uint32_t k = 0; k < LU; k++) {
       const uint32_t r = r0 + k * NT;
       if (r >= n) continue;
-      const uint32_t j = lc[k] >> 16;
-      const uint32_t pos = (j < S ? n - min(sub[j] & 0xFFFFu, n) : n) + (lc[k] & 0xFFFFu);
+      const uint32_t j = lc[k];
+      const uint32_t cnt = (k & 1) ? ix[b][k / 2] >> 16 : ix[b][k / 2] & 0xFFFFu;
+      const uint32_t pos = (j < S ? n - min(sub[j] & 0xFFFFu, n) : n) + cnt;
       if (pos >= n) {
         bad = true;
         continue;
@@ -3474,7 +3516,7 @@ __global__ __launch_bounds__(NT) void k_tour(const uint32_t *__restrict__ link,
                                              uint64_t *__restrict__ max_ts,
                                              uint32_t *__restrict__ perm, uint32_t *__restrict__ vbits,
                                              uint32_t *__restrict__ vcount,
-                                             uint32_t *__restrict__ status, uint32_t *loc,
+                                             uint32_t *__restrict__ status, uint16_t *loc,
                                              unsigned long long *__restrict__ tprof,
                                              uint32_t doc0 = 0) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_t[];
@@ -3500,7 +3542,7 @@ __global__ __launch_bounds__(NT) void k_weave_doc(
     uint32_t *__restrict__ status, uint32_t *__restrict__ big, const uint32_t *__restrict__ doc_log2k,
     uint32_t kbits, uint32_t bm_words, uint32_t *__restrict__ nsc, uint32_t *__restrict__ fcS,
     uint32_t *__restrict__ link, uint32_t *__restrict__ osp, uint32_t *__restrict__ perm,
-    uint32_t *__restrict__ vbits, uint32_t *__restrict__ vcount, uint32_t *loc,
+    uint32_t *__restrict__ vbits, uint32_t *__restrict__ vcount, uint16_t *loc,
     unsigned long long *__restrict__ tprof, uint8_t *__restrict__ site8, uint32_t site_shift,
     uint32_t site_mask) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_w[];
@@ -5216,10 +5258,11 @@ int tail_tour(const Tail &w) {
   const uint64_t D = w.D;
   unsigned long long *tprof = nullptr;
   if (c->tree_prof && alloc_stamps(c, "tprof2", D, 8, &tprof)) return -1;
-  uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", w.N);
+  uint16_t *loc = scratch_t<uint16_t>(c, "tour_loc", w.N);
   if (!loc) return fail(c, "out of device memory (tour)");
   {
-    Launch L(c, "tour", (double)w.N * (4 + 4 + 4 + 1 + 4 + 4));
+    // link, sval, the sublist records out and back 2 + 2, bits, weave_perm
+    Launch L(c, "tour", (double)w.N * (4 + 4 + 2 + 1 + 2 + 4));
     hipLaunchKernelGGL(k_tour<1024>, dim3((uint32_t)D), dim3(1024),
                        (size_t)tour_lds_bytes(t.nmax, t.tour_log2k), c->stream,
                        (const uint32_t *)w.link, w.sval, w.doc_off, w.doc_log2k, w.skey, w.ts_shift,
@@ -5524,7 +5567,7 @@ int front_fused(const ListWeave &w, Front *f) {
   f->skey = w.want_yarns && !f->yarns_fused ? w.skA : nullptr;
   if (f->fused_done) {
     uint32_t *fcS = scratch_t<uint32_t>(c, "fcS", N), *thr = scratch_t<uint32_t>(c, "thr", N);
-    uint32_t *loc = scratch_t<uint32_t>(c, "tour_loc", N);
+    uint16_t *loc = scratch_t<uint16_t>(c, "tour_loc", N);
     if (!fcS || !thr || !loc)
       return fail(c, "out of device memory (fused weave)");
     const uint32_t kbits_t = ceil_log2((uint64_t)t.nmax + 1) + 1;
@@ -5540,11 +5583,11 @@ int front_fused(const ListWeave &w, Front *f) {
     // algorithmic bytes: front end (ids twice, causes, kinds, the rank scratch
     // out and back, par 2, sval 2 or 4, class bitmaps), tree (par 2, kind bits;
     // fcS clear 4, nsc 4; fcS + nsc back 8, link 4), tour (link 4, sval, the
-    // (sublist, index) records out and back 8, weave_perm 4, bits)
+    // sublist records (u16) out and back 4, weave_perm 4, bits)
     const double sv = w.want_yarns ? 4 : 2;
     Launch L(c, "weave", (double)N * (8 + 8 + 8 + 1 + 2 + 2 + 2 + sv + (f->skey ? 16 : 0) + (site8 ? 1 : 0) + 0.25) +
                              (double)N * (2 + 0.25 + 4 + 4 + 8 + 4) +
-                             (double)N * (4 + sv + 8 + 4 + 0.125));
+                             (double)N * (4 + sv + 4 + 4 + 0.125));
     auto launch = [&](auto kern, auto *sv_ptr) {
       hipLaunchKernelGGL(kern, dim3((uint32_t)D), dim3(1024), (size_t)wd_lds, c->stream, w.id_key,
                          w.cause_key, w.kind, w.doc_off, dev_tab(c, "t_tile_first"), FRONT_FUSED_SG, par16,
