@@ -605,6 +605,28 @@ class Weaver:
                        w.max_ts[:D], w.status[:D], None if w.yarn_perm is None else w.yarn_perm[:M])
         return MergeResult(mo, src[:M], w)
 
+    def merge_lists_device(self, a_offsets, a_ptrs, b_offsets, b_ptrs, layout, src_ptr, out_ptrs):
+        """Device-memory call of cw_merge_lists.  a_ptrs / b_ptrs = (id_key,
+        cause_key, kind, value) device pointers; src_ptr: merged_src (uint32
+        [Na+Nb]); out_ptrs as weave_lists_device, every array sized for Na+Nb.
+        Returns the merged offsets (uint64[D+1])."""
+        ao = np.ascontiguousarray(a_offsets, np.uint64)
+        bo = np.ascontiguousarray(b_offsets, np.uint64)
+        if len(ao) != len(bo):
+            raise ValueError("a and b must have the same number of documents")
+        vp = lambda p: C.c_void_p(p) if p else None
+        ba, _ = self._batch(ao, vp(a_ptrs[0]), vp(a_ptrs[1]), vp(a_ptrs[2]), layout)
+        bb, _ = self._batch(bo, vp(b_ptrs[0]), vp(b_ptrs[1]), vp(b_ptrs[2]), layout)
+        mb = CwMergeBatch(ba, vp(a_ptrs[3]), bb, vp(b_ptrs[3]))
+        mo = np.zeros(len(ao), np.uint64)
+        g = lambda n: vp(out_ptrs.get(n))
+        r = CwMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
+                          CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"),
+                                       g("max_ts"), g("status"), g("yarn_perm")))
+        self._check(self._L.cw_merge_lists(self._h, C.byref(mb), C.byref(r), CW_MEM_DEVICE),
+                    "cw_merge_lists")
+        return mo
+
     def weft_lists(self, offsets, id_key, cause_key, kind, layout, cut, yarns=True) -> MergeResult:
         """Host-memory call of cw_weft_lists.  cut: uint64[D << site_bits] packed
         cut id per (document, site rank), 0 = site not named.  Returns the kept

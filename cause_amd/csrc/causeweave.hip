@@ -4497,6 +4497,14 @@ struct cw_ctx {
     const void *lb = nullptr;
     bool ok = false;
   } mmerge;
+  uint32_t list_merge_fused = 1;   // list_merge_fused: one-kernel union stage of cw_merge_lists
+  struct ListMerge {               // the two layouts of the last cw_merge_lists call, as uploaded
+    std::vector<uint64_t> ao, bo;
+    const void *doff = nullptr;    // ... to this buffer
+    bool fits = false;             // every document has na + nb <= LU_MAXDOC
+    uint32_t epoch = 0, lb_docs = 0;  // k_list_union's look-back words' epoch (listmerge.hip)
+    const void *lb = nullptr;
+  } lmerge;
 };
 
 namespace {
@@ -5965,6 +5973,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "exact.hip"
 #include "mappack.hip"
 #include "mapmerge.hip"
+#include "listmerge.hip"
 #include "dist.hip"
 
 namespace {
@@ -6921,26 +6930,27 @@ int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int m
   return 0;
 }
 
+// cw_merge_lists: uploads (host memspace), the union stage (listmerge.hip), one
+// device-to-host copy of the merged offsets, the list weave of the merged
+// documents in device memory, copies out (host memspace).
 int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, int memspace) {
   if (!bt || !res) return fail(c, "null batch/result");
-  if (memspace != CW_MEM_HOST) return fail(c, "cw_merge_lists: only CW_MEM_HOST is supported");
+  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  const bool dev = memspace == CW_MEM_DEVICE;
   const uint64_t D = bt->a.n_docs;
   if (bt->b.n_docs != D) return fail(c, "a and b must have the same number of documents");
   const uint64_t *ao = bt->a.doc_offsets, *bo = bt->b.doc_offsets;
   if (!ao || !bo || ao[0] != 0 || bo[0] != 0) return fail(c, "doc_offsets must start at 0");
+  for (uint64_t d = 0; d < D; d++)
+    if (ao[d + 1] < ao[d] || bo[d + 1] < bo[d]) return fail(c, "doc_offsets not monotone");
   const uint64_t Na = ao[D], Nb = bo[D], NC = Na + Nb;
   if (NC >= 0x7FFFFFFFull) return fail(c, "merge too large: %llu nodes", (unsigned long long)NC);
-  std::vector<uint32_t> h_ao(D + 1), h_bo(D + 1), h_co(D + 1);
-  std::vector<uint64_t> cap(D + 1);
-  for (uint64_t d = 0; d <= D; d++) {
-    if (d < D && (ao[d + 1] < ao[d] || bo[d + 1] < bo[d])) return fail(c, "doc_offsets not monotone");
-    h_ao[d] = (uint32_t)ao[d];
-    h_bo[d] = (uint32_t)bo[d];
-    cap[d] = ao[d] + bo[d];
-    h_co[d] = (uint32_t)cap[d];
+  uint64_t dmax = 0;
+  for (uint64_t d = 0; d < D; d++) {
+    const uint64_t n = (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]);
+    if (n >= LINK_IDX) return fail(c, "document %llu too large", (unsigned long long)d);
+    dmax = std::max(dmax, n);
   }
-  for (uint64_t d = 0; d < D; d++)
-    if (cap[d + 1] - cap[d] >= LINK_IDX) return fail(c, "document %llu too large", (unsigned long long)d);
   cw_list_result &W = res->weave;
   if (!res->merged_offsets || !res->merged_src || !W.weave_perm || !W.visible_count || !W.status)
     return fail(c, "merged_offsets, merged_src, weave_perm, visible_count and status are required");
@@ -6948,121 +6958,148 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
       (Nb && (!bt->b.id_key || !bt->b.cause_key || !bt->b.kind || !bt->b_value)))
     return fail(c, "null input arrays");
   HIPCHK(c, hipSetDevice(c->device));
-  const size_t NCs = std::max<uint64_t>(NC, 1);
-  uint64_t *aid = scratch_t<uint64_t>(c, "g_aid", std::max<uint64_t>(Na, 1)),
-           *aca = scratch_t<uint64_t>(c, "g_aca", std::max<uint64_t>(Na, 1)),
-           *ava = scratch_t<uint64_t>(c, "g_ava", std::max<uint64_t>(Na, 1));
-  uint64_t *bid = scratch_t<uint64_t>(c, "g_bid", std::max<uint64_t>(Nb, 1)),
-           *bca = scratch_t<uint64_t>(c, "g_bca", std::max<uint64_t>(Nb, 1)),
-           *bva = scratch_t<uint64_t>(c, "g_bva", std::max<uint64_t>(Nb, 1));
-  uint8_t *akd = scratch_t<uint8_t>(c, "g_akd", std::max<uint64_t>(Na, 1)),
-          *bkd = scratch_t<uint8_t>(c, "g_bkd", std::max<uint64_t>(Nb, 1));
-  uint32_t *dao = scratch_t<uint32_t>(c, "g_aoff", D + 1), *dbo = scratch_t<uint32_t>(c, "g_boff", D + 1),
-           *dco = scratch_t<uint32_t>(c, "g_coff", D + 1), *dmo = scratch_t<uint32_t>(c, "g_moff", D + 1);
-  uint64_t *cid = scratch_t<uint64_t>(c, "g_cid", NCs), *cca = scratch_t<uint64_t>(c, "g_cca", NCs),
-           *cva = scratch_t<uint64_t>(c, "g_cva", NCs);
-  uint8_t *ckd = scratch_t<uint8_t>(c, "g_ckd", NCs);
-  uint64_t *mid = scratch_t<uint64_t>(c, "g_mid", NCs), *mca = scratch_t<uint64_t>(c, "g_mca", NCs);
-  uint8_t *mkd = scratch_t<uint8_t>(c, "g_mkd", NCs);
-  uint32_t *msrc = scratch_t<uint32_t>(c, "g_msrc", NCs), *mcnt = scratch_t<uint32_t>(c, "g_mcnt", D + 1),
-           *mst = scratch_t<uint32_t>(c, "g_mst", D + 1);
-  uint64_t *uskA = scratch_t<uint64_t>(c, "g_skA", NCs), *uskB = scratch_t<uint64_t>(c, "g_skB", NCs);
-  uint32_t *usvA = scratch_t<uint32_t>(c, "g_svA", NCs), *usvB = scratch_t<uint32_t>(c, "g_svB", NCs);
-  if (!aid || !aca || !ava || !bid || !bca || !bva || !akd || !bkd || !dao || !dbo || !dco || !dmo ||
-      !cid || !cca || !cva || !ckd || !mid || !mca || !mkd || !msrc || !mcnt || !mst || !uskA ||
-      !uskB || !usvA || !usvB)
-    return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (Na) {
-    HIPCHK(c, hipMemcpy(aid, bt->a.id_key, Na * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(aca, bt->a.cause_key, Na * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ava, bt->a_value, Na * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(akd, bt->a.kind, Na, hipMemcpyHostToDevice));
-  }
-  if (Nb) {
-    HIPCHK(c, hipMemcpy(bid, bt->b.id_key, Nb * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(bca, bt->b.cause_key, Nb * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(bva, bt->b_value, Nb * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(bkd, bt->b.kind, Nb, hipMemcpyHostToDevice));
-  }
-  HIPCHK(c, hipMemcpy(dao, h_ao.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dbo, h_bo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(dco, h_co.data(), (D + 1) * 4, hipMemcpyHostToDevice));
   if (!grid_ok(D, 1024)) return fail(c, "batch too large for one dispatch");
   uint64_t *mo = res->merged_offsets;
-  mo[0] = 0;
-  if (NC == 0) {
-    for (uint64_t d = 0; d < D; d++) {
-      mo[d + 1] = 0;
-      W.status[d] = CW_STATUS_ROOT;
-      W.visible_count[d] = 0;
-      if (W.max_ts) W.max_ts[d] = 0;
+  if (NC == 0) {  // nothing to unite: every document is empty (no root)
+    for (uint64_t d = 0; d <= D; d++) mo[d] = 0;
+    if (!dev) {
+      for (uint64_t d = 0; d < D; d++) {
+        W.status[d] = CW_STATUS_ROOT;
+        W.visible_count[d] = 0;
+        if (W.max_ts) W.max_ts[d] = 0;
+      }
+    } else if (D) {
+      hipLaunchKernelGGL(k_fill_u32, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, W.status,
+                         (uint32_t)CW_STATUS_ROOT, (uint32_t)D);
+      if (check_launch(c, "fill_status")) return -1;
+      HIPCHK(c, hipMemsetAsync(W.visible_count, 0, D * 4, c->stream));
+      if (W.max_ts) HIPCHK(c, hipMemsetAsync(W.max_ts, 0, D * 8, c->stream));
+      if (!c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return 0;
   }
-  // 1. union: a then b per document, in capacity slots
-  hipLaunchKernelGGL(k_merge_concat, dim3((uint32_t)D), dim3(256), 0, c->stream, aid, aca, akd,
-                     ava, bid, bca, bkd, bva, dao, dbo, dco, cid, cca, ckd, cva);
-  if (check_launch(c, "merge_concat")) return -1;
-  // 2. id order per capacity slot (the general segmented radix sort)
-  if (ensure_tables(c, D, cap.data())) return -1;
-  uint32_t key_bits = bt->a.key_bits;
-  if (key_bits == 0 && find_key_bits(c, cid, (uint32_t)NC, &key_bits)) return -1;
-  uint64_t *skey;
-  uint32_t *sval;
-  if (radix_sort<uint64_t>(c, "m_idsort", cid, nullptr, uskA, usvA, uskB, usvB, key_bits, 0,
-                           (uint32_t)NC, &skey, &sval))
-    return -1;
-  // 3. dedup: count, offsets, write
-  hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval,
-                     cca, ckd, cva, dco, 0, mcnt, dmo, mid, mca, mkd, msrc, mst);
-  if (check_launch(c, "merge_count")) return -1;
-  std::vector<uint32_t> h_cnt(D);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
-  std::vector<uint32_t> h_mo(D + 1);
-  for (uint64_t d = 0; d < D; d++) {
-    mo[d + 1] = mo[d] + h_cnt[d];
-    h_mo[d] = (uint32_t)mo[d];
+  const size_t NCs = NC;
+  LuHost h{};
+  h.D = D;
+  h.Na = Na;
+  h.Nb = Nb;
+  h.ao = ao;
+  h.bo = bo;
+  h.key_bits = bt->a.key_bits;
+  h.a = LuSide{bt->a.id_key, bt->a.cause_key, bt->a_value, bt->a.kind, nullptr};
+  h.b = LuSide{bt->b.id_key, bt->b.cause_key, bt->b_value, bt->b.kind, nullptr};
+  if (!dev) {  // uploads
+    uint64_t *aid = scratch_t<uint64_t>(c, "g_aid", Na), *aca = scratch_t<uint64_t>(c, "g_aca", Na),
+             *ava = scratch_t<uint64_t>(c, "g_ava", Na);
+    uint64_t *bid = scratch_t<uint64_t>(c, "g_bid", Nb), *bca = scratch_t<uint64_t>(c, "g_bca", Nb),
+             *bva = scratch_t<uint64_t>(c, "g_bva", Nb);
+    uint8_t *akd = scratch_t<uint8_t>(c, "g_akd", Na), *bkd = scratch_t<uint8_t>(c, "g_bkd", Nb);
+    if (!aid || !aca || !ava || !bid || !bca || !bva || !akd || !bkd)
+      return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (Na) {
+      HIPCHK(c, hipMemcpy(aid, bt->a.id_key, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(aca, bt->a.cause_key, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(ava, bt->a_value, Na * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(akd, bt->a.kind, Na, hipMemcpyHostToDevice));
+    }
+    if (Nb) {
+      HIPCHK(c, hipMemcpy(bid, bt->b.id_key, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bca, bt->b.cause_key, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bva, bt->b_value, Nb * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(bkd, bt->b.kind, Nb, hipMemcpyHostToDevice));
+    }
+    h.a = LuSide{aid, aca, ava, akd, nullptr};
+    h.b = LuSide{bid, bca, bva, bkd, nullptr};
   }
-  h_mo[D] = (uint32_t)mo[D];
-  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval,
-                     cca, ckd, cva, dco, 1, mcnt, dmo, mid, mca, mkd, msrc, mst);
-  if (check_launch(c, "merge_write")) return -1;
-  // 4. the merged documents through the list pipeline
+  // the two layouts and the capacity slots on the device, cached while they repeat
+  {
+    auto &lm = c->lmerge;
+    uint32_t *dao = scratch_t<uint32_t>(c, "g_aoff", D + 1), *dbo = scratch_t<uint32_t>(c, "g_boff", D + 1),
+             *dco = scratch_t<uint32_t>(c, "g_coff", D + 1);
+    if (!dao || !dbo || !dco) return fail(c, "out of device memory (merge offsets)");
+    const bool same = lm.doff == dao && lm.ao.size() == D + 1 && lm.bo.size() == D + 1 &&
+                      memcmp(lm.ao.data(), ao, (D + 1) * 8) == 0 &&
+                      memcmp(lm.bo.data(), bo, (D + 1) * 8) == 0;
+    if (!same) {
+      std::vector<uint32_t> h_ao(D + 1), h_bo(D + 1), h_co(D + 1);
+      for (uint64_t d = 0; d <= D; d++) {
+        h_ao[d] = (uint32_t)ao[d];
+        h_bo[d] = (uint32_t)bo[d];
+        h_co[d] = (uint32_t)(ao[d] + bo[d]);
+      }
+      lm.ao.clear();
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipMemcpy(dao, h_ao.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dbo, h_bo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dco, h_co.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+      lm.ao.assign(ao, ao + D + 1);
+      lm.bo.assign(bo, bo + D + 1);
+      lm.doff = dao;
+      lm.fits = dmax <= LU_MAXDOC;
+    }
+    h.a.off = dao;
+    h.b.off = dbo;
+    h.coff = dco;
+  }
+  // the merged documents (device) and the union status
+  h.mid = scratch_t<uint64_t>(c, "g_mid", NCs);
+  h.mca = scratch_t<uint64_t>(c, "g_mca", NCs);
+  h.mkd = scratch_t<uint8_t>(c, "g_mkd", NCs);
+  h.msrc = dev ? res->merged_src : scratch_t<uint32_t>(c, "g_msrc", NCs);
+  h.mst = scratch_t<uint32_t>(c, "g_mst", D + 1);
+  if (!h.mid || !h.mca || !h.mkd || !h.msrc || !h.mst)
+    return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
+  const uint64_t *dmo64 = nullptr;
+  const uint32_t *dmo32 = nullptr;
+  {
+    int rc = 1;
+    if (c->list_merge_fused) rc = list_union_fused(c, h, mo, &dmo64);
+    if (rc == 1) rc = list_union_general(c, h, mo, &dmo32);  // one oversize document: the whole call
+    if (rc) return -1;
+  }
+  // the merged documents through the list pipeline, in device memory
   const uint64_t NM = mo[D];
   if (ensure_tables(c, D, mo)) return -1;
   cw_list_batch lb = bt->a;
   lb.doc_offsets = mo;
-  lb.key_bits = key_bits;
-  cw_list_result lr{};
-  lr.weave_perm = scratch_t<uint32_t>(c, "g_perm", NCs);
-  lr.visible_bits = W.visible_bits ? scratch_t<uint32_t>(c, "g_bits", (NCs + 31) / 32) : nullptr;
-  lr.visible_count = scratch_t<uint32_t>(c, "g_vc", D + 1);
-  lr.max_ts = W.max_ts ? scratch_t<uint64_t>(c, "g_mts", D + 1) : nullptr;
-  lr.status = scratch_t<uint32_t>(c, "g_st", D + 1);
-  lr.yarn_perm = W.yarn_perm ? scratch_t<uint32_t>(c, "g_yarn", NCs) : nullptr;
-  if (!lr.weave_perm || !lr.visible_count || !lr.status || (W.visible_bits && !lr.visible_bits) ||
-      (W.max_ts && !lr.max_ts) || (W.yarn_perm && !lr.yarn_perm))
-    return fail(c, "out of device memory (merge outputs)");
-  if (weave_lists_device(c, &lb, mid, mca, mkd, &lr)) return -1;
-  if (exact_fixup(c, &lb, mid, mca, mkd, &lr, c->x_hint)) return -1;
-  hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, mst,
-                     lr.status, (uint32_t)D);
-  if (check_launch(c, "or_status")) return -1;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(res->merged_src, msrc, NM * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(W.weave_perm, lr.weave_perm, NM * 4, hipMemcpyDeviceToHost));
-  if (W.visible_bits)
-    HIPCHK(c, hipMemcpy(W.visible_bits, lr.visible_bits, (NM + 31) / 32 * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(W.visible_count, lr.visible_count, D * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(W.status, lr.status, D * 4, hipMemcpyDeviceToHost));
-  if (W.max_ts) HIPCHK(c, hipMemcpy(W.max_ts, lr.max_ts, D * 8, hipMemcpyDeviceToHost));
-  if (W.yarn_perm) HIPCHK(c, hipMemcpy(W.yarn_perm, lr.yarn_perm, NM * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipDeviceSynchronize());
-  for (uint64_t d = 0; d < D; d++)
-    if (mo[d + 1] == mo[d]) W.status[d] |= CW_STATUS_ROOT;
+  lb.key_bits = h.key_bits;
+  cw_list_result lr = W;
+  if (!dev) {
+    lr.weave_perm = scratch_t<uint32_t>(c, "g_perm", NCs);
+    lr.visible_bits = W.visible_bits ? scratch_t<uint32_t>(c, "g_bits", (NCs + 31) / 32) : nullptr;
+    lr.visible_count = scratch_t<uint32_t>(c, "g_vc", D + 1);
+    lr.max_ts = W.max_ts ? scratch_t<uint64_t>(c, "g_mts", D + 1) : nullptr;
+    lr.status = scratch_t<uint32_t>(c, "g_st", D + 1);
+    lr.yarn_perm = W.yarn_perm ? scratch_t<uint32_t>(c, "g_yarn", NCs) : nullptr;
+    if (!lr.weave_perm || !lr.visible_count || !lr.status || (W.visible_bits && !lr.visible_bits) ||
+        (W.max_ts && !lr.max_ts) || (W.yarn_perm && !lr.yarn_perm))
+      return fail(c, "out of device memory (merge outputs)");
+  }
+  if (weave_lists_device(c, &lb, h.mid, h.mca, h.mkd, &lr)) return -1;
+  if (exact_fixup(c, &lb, h.mid, h.mca, h.mkd, &lr, c->x_hint)) return -1;
+  // the union's DUP and the merged-empty documents' ROOT join the weave's bits
+  if (dmo64)
+    hipLaunchKernelGGL((k_merge_status<uint64_t>), dim3((uint32_t)((D + 255) / 256)), dim3(256), 0,
+                       c->stream, h.mst, dmo64, lr.status, (uint32_t)D);
+  else
+    hipLaunchKernelGGL((k_merge_status<uint32_t>), dim3((uint32_t)((D + 255) / 256)), dim3(256), 0,
+                       c->stream, h.mst, dmo32, lr.status, (uint32_t)D);
+  if (check_launch(c, "merge_status")) return -1;
+  if (!dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(res->merged_src, h.msrc, NM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(W.weave_perm, lr.weave_perm, NM * 4, hipMemcpyDeviceToHost));
+    if (W.visible_bits)
+      HIPCHK(c, hipMemcpy(W.visible_bits, lr.visible_bits, (NM + 31) / 32 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(W.visible_count, lr.visible_count, D * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(W.status, lr.status, D * 4, hipMemcpyDeviceToHost));
+    if (W.max_ts) HIPCHK(c, hipMemcpy(W.max_ts, lr.max_ts, D * 8, hipMemcpyDeviceToHost));
+    if (W.yarn_perm) HIPCHK(c, hipMemcpy(W.yarn_perm, lr.yarn_perm, NM * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipDeviceSynchronize());
+  } else if (!c->async) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   if (c->prof) return collect_prof(c);
   return 0;
 }
@@ -7389,6 +7426,7 @@ static const struct {
     {"map_small", &cw_ctx::map_small, 0, UINT32_MAX},
     {"map_fused", &cw_ctx::map_fused, 0, UINT32_MAX},
     {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
+    {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
     {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
 };

@@ -111,6 +111,11 @@ int cw_ctx_set_stream(cw_ctx *ctx, void *hip_stream);
  *    flag; one giant document (>= 2^22 nodes) waits for its 4-byte status.
  *  - cw_weave_maps, cw_partition_keys and the out-of-domain (exact) path read
  *    back counts they size later launches with.
+ *  - cw_merge_lists (device memory) waits once for the merged offsets and the
+ *    union kernel's control word -- they are the doc_offsets of the weave that
+ *    follows -- and then for whatever cw_weave_lists itself waits for; when the
+ *    two layouts differ from the previous call's it also uploads them with
+ *    blocking copies.  The general union waits for its counts as well.
  * A caller that wants to overlap host work with the weave should run it on
  * its own thread or queue the weave behind no other work. */
 int cw_ctx_set_async(cw_ctx *ctx, int async);
@@ -313,7 +318,22 @@ typedef struct {
                                holds doc-local merged indices (into merged_src)      */
 } cw_merge_result;
 
-/* Host memory only (memspace must be CW_MEM_HOST in this version). */
+/* memspace: where the node arrays of a and b, a_value, b_value, merged_src and
+ * the arrays of `weave` live; the two doc_offsets and merged_offsets are always
+ * host memory.  In device memory nothing is uploaded and merged_src and the
+ * weave arrays are written in place (the CW_STATUS_ROOT bit of a document whose
+ * merged size is 0 included).
+ * Limits: Na + Nb < 2^31 - 1; per document na + nb below cw_weave_lists' limit
+ * for a batch of several documents.  Empty documents, on one side or both, are
+ * legal (a merged size of 0 sets CW_STATUS_ROOT: no root).
+ * When every document has na + nb <= 65,535 the union is one kernel, a
+ * workgroup per document (listmerge.hip): Lamport ids are dense, so a bitmap
+ * over the ids ranks them and nothing is sorted.  One larger document sends the
+ * whole call through the general union (concatenation, a segmented sort and
+ * two dedup passes around a host scan); so does a document whose ids lie past
+ * the bitmap (packed ids >= 245,760: sparse timestamps, wide layouts, ids >=
+ * 2^63) or that repeats an id inside one side -- the kernel notices, and the
+ * call is rerun on the general union.  Both give the same arrays. */
 int cw_merge_lists(cw_ctx *ctx, const cw_merge_batch *batch, cw_merge_result *result,
                    int memspace);
 
