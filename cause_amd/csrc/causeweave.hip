@@ -43,6 +43,7 @@
 
 #include "causeweave.h"
 #include "cw_internal.h"
+#include "lookback.h"
 
 using namespace cw;
 
@@ -4481,8 +4482,7 @@ struct cw_ctx {
     std::vector<uint64_t> off;
     std::vector<uint32_t> doc0;
     uint32_t dbits = 0, pk = 0, dmax = 1;  // (dmax: most collections in one pack)
-    uint32_t epoch = 0, lb_packs = 0;      // look-back words' epoch (mappack.hip)
-    const void *lb = nullptr;
+    LookBack lb;                   // k_map_pack's look-back words
     uint64_t maxcoll = 0;          // the largest collection of the cached layout
     bool ok = false;
     bool same = false;             // this call's coll_offsets equal off (set by cw_weave_maps)
@@ -4493,8 +4493,7 @@ struct cw_ctx {
     std::vector<uint64_t> ao, bo;
     std::vector<uint32_t> doc0;
     uint32_t pk = 0, dmax = 1;
-    uint32_t epoch = 0, lb_packs = 0;  // its own look-back words' epoch (mapmerge.hip)
-    const void *lb = nullptr;
+    LookBack lb;                   // k_map_union's look-back words
     bool ok = false;
   } mmerge;
   uint32_t list_merge_fused = 1;   // list_merge_fused: one-kernel union stage of cw_merge_lists
@@ -4502,8 +4501,7 @@ struct cw_ctx {
     std::vector<uint64_t> ao, bo;
     const void *doff = nullptr;    // ... to this buffer
     bool fits = false;             // every document has na + nb <= LU_MAXDOC
-    uint32_t epoch = 0, lb_docs = 0;  // k_list_union's look-back words' epoch (listmerge.hip)
-    const void *lb = nullptr;
+    LookBack lb;                   // k_list_union's look-back words
   } lmerge;
 };
 
@@ -4561,15 +4559,40 @@ hipEvent_t get_event(cw_ctx *c) {
   return e;
 }
 
-// Launch helper: optional per-kernel event timing on the launch stream.
+// The look-back words of a one-kernel stage (lookback.h): `words` words of the
+// scratch buffer `name`, cleared on the stream when lb_step says so, and the
+// first of this call's `epochs` epochs.  nullptr on error.
+unsigned long long *lookback_words(cw_ctx *c, LookBack &s, const char *name, uint32_t words,
+                                   uint32_t epochs, uint32_t *epoch) {
+  unsigned long long *lb = scratch_t<unsigned long long>(c, name, words);
+  if (!lb) {
+    fail(c, "out of device memory (%s)", name);
+    return nullptr;
+  }
+  const LbStep st = lb_step(s, lb, words, epochs);
+  if (st.clear && hipMemsetAsync(lb, 0, (size_t)words * 8, c->stream) != hipSuccess) {
+    fail(c, "hipMemsetAsync (%s)", name);
+    return nullptr;
+  }
+  s = st.next;
+  *epoch = st.first;
+  return lb;
+}
+
+// Launch helper: optional per-kernel event timing on the launch stream.  `rec`
+// (optional) receives the index of the launch's record in c->pending, pushed
+// when the Launch goes out of scope; it is left alone when there is no record
+// (profiling off, or prof_only names another stat).
+constexpr size_t NO_REC = (size_t)-1;
 struct Launch {
   cw_ctx *c;
   const char *name;
   double bytes;
   hipStream_t s;
+  size_t *rec;
   hipEvent_t a = nullptr;
-  Launch(cw_ctx *c_, const char *n, double by, hipStream_t st = nullptr)
-      : c(c_), name(n), bytes(by), s(st ? st : c_->stream) {
+  Launch(cw_ctx *c_, const char *n, double by, hipStream_t st = nullptr, size_t *rec_ = nullptr)
+      : c(c_), name(n), bytes(by), s(st ? st : c_->stream), rec(rec_) {
     if (c->prof && (c->prof_only.empty() || c->prof_only == n)) {
       a = get_event(c);
       (void)hipEventRecord(a, s);
@@ -4579,6 +4602,7 @@ struct Launch {
     if (c->prof && a) {
       hipEvent_t b = get_event(c);
       (void)hipEventRecord(b, s);
+      if (rec) *rec = c->pending.size();
       c->pending.push_back({name, a, b, bytes});
     }
   }
@@ -4618,6 +4642,26 @@ uint32_t ceil_log2(uint64_t x) {
   uint32_t r = 0;
   while ((1ull << r) < x) r++;
   return r;
+}
+
+// A pack table: runs of whole consecutive documents of at most pk nodes in all
+// (document d has ao[d+1] - ao[d] nodes, plus b's when bo is given) and at most
+// max_docs documents.  doc0 = each run's first document, then D; *dmax = the
+// most documents in a run.  false (the table unfinished): a document alone
+// has more than pk nodes.
+bool pack_runs(uint64_t D, const uint64_t *ao, const uint64_t *bo, uint64_t pk, uint64_t max_docs,
+               std::vector<uint32_t> &doc0, uint32_t *dmax) {
+  doc0.clear();
+  *dmax = 0;
+  for (uint64_t d = 0; d < D;) {
+    const uint64_t s = d;
+    while (d < D && (ao[d + 1] - ao[s]) + (bo ? bo[d + 1] - bo[s] : 0) <= pk && d - s < max_docs) d++;
+    if (d == s) return false;
+    doc0.push_back((uint32_t)s);
+    *dmax = std::max(*dmax, (uint32_t)(d - s));
+  }
+  doc0.push_back((uint32_t)D);
+  return true;
 }
 
 // Host tables: tiles (sort/pass grids), splitter blocks and walker blocks.
@@ -4742,17 +4786,7 @@ void build_tables(cw_ctx *c, uint64_t D, const uint64_t *off, bool giant) {
   // (only used when every document fits one tile)
   t.pack_doc0.clear();
   t.pack_dmax = 0;
-  if (t.nmax <= TILE) {
-    uint64_t d = 0;
-    while (d < D) {
-      const uint64_t d0 = d;
-      while (d < D && off[d + 1] - off[d0] <= TILE) d++;
-      if (d == d0) d++;  // (cannot happen: every document <= TILE)
-      t.pack_doc0.push_back((uint32_t)d0);
-      t.pack_dmax = std::max(t.pack_dmax, (uint32_t)(d - d0));
-    }
-    t.pack_doc0.push_back((uint32_t)D);
-  }
+  if (t.nmax <= TILE) (void)pack_runs(D, off, nullptr, TILE, D, t.pack_doc0, &t.pack_dmax);
   t.bkt_off[D] = stot;
   t.Btot = stot;
   t.T = (uint32_t)t.tile_doc.size();
@@ -6930,27 +6964,56 @@ int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int m
   return 0;
 }
 
+// The two sides of a merge call, checked before anything is read from the
+// arrays: `unit` and `field` name the unit and its offsets in the texts, a unit
+// has fewer than `limit` nodes (na + nb).  *largest (optional): the largest unit.
+uint64_t n_units(const cw_list_batch &b) { return b.n_docs; }
+uint64_t n_units(const cw_map_batch &b) { return b.n_colls; }
+const uint64_t *unit_offsets(const cw_list_batch &b) { return b.doc_offsets; }
+const uint64_t *unit_offsets(const cw_map_batch &b) { return b.coll_offsets; }
+template <typename B>
+int check_merge_sides(cw_ctx *c, const B *bt, const void *res, int memspace, const char *unit,
+                      const char *field, uint64_t limit, uint64_t *largest) {
+  if (!bt || !res) return fail(c, "null batch/result");
+  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  const uint64_t D = n_units(bt->a), *ao = unit_offsets(bt->a), *bo = unit_offsets(bt->b);
+  if (n_units(bt->b) != D) return fail(c, "a and b must have the same number of %ss", unit);
+  if (!ao || !bo) return fail(c, "%s is required (host memory)", field);
+  if (ao[0] != 0 || bo[0] != 0) return fail(c, "%s must start at 0", field);
+  for (uint64_t d = 0; d < D; d++)
+    if (ao[d + 1] < ao[d] || bo[d + 1] < bo[d]) return fail(c, "%s not monotone", field);
+  const uint64_t NC = ao[D] + bo[D];
+  if (NC >= 0x7FFFFFFFull) return fail(c, "merge too large: %llu nodes (limit 2^31-1)", (unsigned long long)NC);
+  uint64_t mx = 0;  // (asked for by the lists only: the maximum costs a 10^6-collection call 0.1 ms)
+  for (uint64_t d = 0; d < D; d++) {
+    const uint64_t n = (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]);
+    if (n >= limit) return fail(c, "%s %llu too large", unit, (unsigned long long)d);
+    if (largest) mx = std::max(mx, n);
+  }
+  if (largest) *largest = mx;
+  return 0;
+}
+
+// A host array in the scratch buffer `name`: *dst = the device copy (nothing is
+// copied when bytes == 0).  The stream is idle (the caller's wait).
+template <typename T>
+int upload(cw_ctx *c, const char *name, const T *src, size_t bytes, const T **dst) {
+  void *p = scratch(c, name, bytes);
+  if (!p) return fail(c, "out of device memory (%s, %zu bytes)", name, bytes);
+  if (bytes) HIPCHK(c, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+  *dst = static_cast<const T *>(p);
+  return 0;
+}
+
 // cw_merge_lists: uploads (host memspace), the union stage (listmerge.hip), one
 // device-to-host copy of the merged offsets, the list weave of the merged
 // documents in device memory, copies out (host memspace).
 int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, int memspace) {
-  if (!bt || !res) return fail(c, "null batch/result");
-  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  uint64_t dmax;
+  if (check_merge_sides(c, bt, res, memspace, "document", "doc_offsets", LINK_IDX, &dmax)) return -1;
   const bool dev = memspace == CW_MEM_DEVICE;
-  const uint64_t D = bt->a.n_docs;
-  if (bt->b.n_docs != D) return fail(c, "a and b must have the same number of documents");
-  const uint64_t *ao = bt->a.doc_offsets, *bo = bt->b.doc_offsets;
-  if (!ao || !bo || ao[0] != 0 || bo[0] != 0) return fail(c, "doc_offsets must start at 0");
-  for (uint64_t d = 0; d < D; d++)
-    if (ao[d + 1] < ao[d] || bo[d + 1] < bo[d]) return fail(c, "doc_offsets not monotone");
+  const uint64_t D = bt->a.n_docs, *ao = bt->a.doc_offsets, *bo = bt->b.doc_offsets;
   const uint64_t Na = ao[D], Nb = bo[D], NC = Na + Nb;
-  if (NC >= 0x7FFFFFFFull) return fail(c, "merge too large: %llu nodes", (unsigned long long)NC);
-  uint64_t dmax = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    const uint64_t n = (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]);
-    if (n >= LINK_IDX) return fail(c, "document %llu too large", (unsigned long long)d);
-    dmax = std::max(dmax, n);
-  }
   cw_list_result &W = res->weave;
   if (!res->merged_offsets || !res->merged_src || !W.weave_perm || !W.visible_count || !W.status)
     return fail(c, "merged_offsets, merged_src, weave_perm, visible_count and status are required");
@@ -6989,28 +7052,16 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   h.a = LuSide{bt->a.id_key, bt->a.cause_key, bt->a_value, bt->a.kind, nullptr};
   h.b = LuSide{bt->b.id_key, bt->b.cause_key, bt->b_value, bt->b.kind, nullptr};
   if (!dev) {  // uploads
-    uint64_t *aid = scratch_t<uint64_t>(c, "g_aid", Na), *aca = scratch_t<uint64_t>(c, "g_aca", Na),
-             *ava = scratch_t<uint64_t>(c, "g_ava", Na);
-    uint64_t *bid = scratch_t<uint64_t>(c, "g_bid", Nb), *bca = scratch_t<uint64_t>(c, "g_bca", Nb),
-             *bva = scratch_t<uint64_t>(c, "g_bva", Nb);
-    uint8_t *akd = scratch_t<uint8_t>(c, "g_akd", Na), *bkd = scratch_t<uint8_t>(c, "g_bkd", Nb);
-    if (!aid || !aca || !ava || !bid || !bca || !bva || !akd || !bkd)
-      return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Na) {
-      HIPCHK(c, hipMemcpy(aid, bt->a.id_key, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(aca, bt->a.cause_key, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(ava, bt->a_value, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(akd, bt->a.kind, Na, hipMemcpyHostToDevice));
-    }
-    if (Nb) {
-      HIPCHK(c, hipMemcpy(bid, bt->b.id_key, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bca, bt->b.cause_key, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bva, bt->b_value, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bkd, bt->b.kind, Nb, hipMemcpyHostToDevice));
-    }
-    h.a = LuSide{aid, aca, ava, akd, nullptr};
-    h.b = LuSide{bid, bca, bva, bkd, nullptr};
+    if (upload(c, "g_aid", bt->a.id_key, Na * 8, &h.a.id) ||
+        upload(c, "g_aca", bt->a.cause_key, Na * 8, &h.a.cause) ||
+        upload(c, "g_ava", bt->a_value, Na * 8, &h.a.val) ||
+        upload(c, "g_akd", bt->a.kind, Na, &h.a.kind) ||
+        upload(c, "g_bid", bt->b.id_key, Nb * 8, &h.b.id) ||
+        upload(c, "g_bca", bt->b.cause_key, Nb * 8, &h.b.cause) ||
+        upload(c, "g_bva", bt->b_value, Nb * 8, &h.b.val) ||
+        upload(c, "g_bkd", bt->b.kind, Nb, &h.b.kind))
+      return -1;
   }
   // the two layouts and the capacity slots on the device, cached while they repeat
   {
@@ -7109,21 +7160,10 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
 // on the merged arrays, copies out.  The merged arrays have scratch names of
 // their own (mm_*): weave_maps_impl reuses skA / svA / m_* and the sort's.
 int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result *res, int memspace) {
-  if (!bt || !res) return fail(c, "null batch/result");
-  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  if (check_merge_sides(c, bt, res, memspace, "collection", "coll_offsets", LINK_IDX - 1, nullptr)) return -1;
   const bool dev = memspace == CW_MEM_DEVICE;
-  const uint64_t D = bt->a.n_colls;
-  if (bt->b.n_colls != D) return fail(c, "a and b must have the same number of collections");
-  const uint64_t *ao = bt->a.coll_offsets, *bo = bt->b.coll_offsets;
-  if (!ao || !bo) return fail(c, "coll_offsets is required (host memory)");
-  if (ao[0] != 0 || bo[0] != 0) return fail(c, "coll_offsets[0] must be 0");
-  for (uint64_t d = 0; d < D; d++)
-    if (ao[d + 1] < ao[d] || bo[d + 1] < bo[d]) return fail(c, "coll_offsets not monotone");
+  const uint64_t D = bt->a.n_colls, *ao = bt->a.coll_offsets, *bo = bt->b.coll_offsets;
   const uint64_t Na = ao[D], Nb = bo[D], NC = Na + Nb;
-  if (NC >= 0x7FFFFFFFull) return fail(c, "merge too large: %llu nodes (limit 2^31-1)", (unsigned long long)NC);
-  for (uint64_t d = 0; d < D; d++)
-    if ((ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]) >= LINK_IDX - 1)
-      return fail(c, "collection %llu too large", (unsigned long long)d);
   cw_map_result &M = res->maps;
   if (!res->merged_offsets || !res->merged_src || !M.seg_offsets || !M.seg_coll || !M.seg_key ||
       !M.seg_active || !M.seg_perm || !M.status)
@@ -7145,31 +7185,18 @@ int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result
   h.a = MuSide{bt->a.id_key, bt->a.cause, bt->a_value, bt->a.cause_is_id, bt->a.kind, nullptr, nullptr};
   h.b = MuSide{bt->b.id_key, bt->b.cause, bt->b_value, bt->b.cause_is_id, bt->b.kind, nullptr, nullptr};
   if (!dev && NC) {  // uploads
-    uint64_t *ai = scratch_t<uint64_t>(c, "mm_aid", Na), *ac = scratch_t<uint64_t>(c, "mm_aca", Na),
-             *av = scratch_t<uint64_t>(c, "mm_ava", Na);
-    uint64_t *bi = scratch_t<uint64_t>(c, "mm_bid", Nb), *bc = scratch_t<uint64_t>(c, "mm_bca", Nb),
-             *bv = scratch_t<uint64_t>(c, "mm_bva", Nb);
-    uint8_t *as = scratch_t<uint8_t>(c, "mm_acis", Na), *ak = scratch_t<uint8_t>(c, "mm_akd", Na),
-            *bs = scratch_t<uint8_t>(c, "mm_bcis", Nb), *bk = scratch_t<uint8_t>(c, "mm_bkd", Nb);
-    if (!ai || !ac || !av || !bi || !bc || !bv || !as || !ak || !bs || !bk)
-      return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (Na) {
-      HIPCHK(c, hipMemcpy(ai, bt->a.id_key, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(ac, bt->a.cause, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(av, bt->a_value, Na * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(as, bt->a.cause_is_id, Na, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(ak, bt->a.kind, Na, hipMemcpyHostToDevice));
-    }
-    if (Nb) {
-      HIPCHK(c, hipMemcpy(bi, bt->b.id_key, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bc, bt->b.cause, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bv, bt->b_value, Nb * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bs, bt->b.cause_is_id, Nb, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(bk, bt->b.kind, Nb, hipMemcpyHostToDevice));
-    }
-    h.a = MuSide{ai, ac, av, as, ak, nullptr, nullptr};
-    h.b = MuSide{bi, bc, bv, bs, bk, nullptr, nullptr};
+    if (upload(c, "mm_aid", bt->a.id_key, Na * 8, &h.a.id) ||
+        upload(c, "mm_aca", bt->a.cause, Na * 8, &h.a.cause) ||
+        upload(c, "mm_ava", bt->a_value, Na * 8, &h.a.val) ||
+        upload(c, "mm_acis", bt->a.cause_is_id, Na, &h.a.cis) ||
+        upload(c, "mm_akd", bt->a.kind, Na, &h.a.kind) ||
+        upload(c, "mm_bid", bt->b.id_key, Nb * 8, &h.b.id) ||
+        upload(c, "mm_bca", bt->b.cause, Nb * 8, &h.b.cause) ||
+        upload(c, "mm_bva", bt->b_value, Nb * 8, &h.b.val) ||
+        upload(c, "mm_bcis", bt->b.cause_is_id, Nb, &h.b.cis) ||
+        upload(c, "mm_bkd", bt->b.kind, Nb, &h.b.kind))
+      return -1;
   }
   // the merged collections (device) and the union status
   uint64_t *mid = scratch_t<uint64_t>(c, "mm_id", NC), *mca = scratch_t<uint64_t>(c, "mm_cause", NC);

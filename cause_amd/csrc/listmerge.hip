@@ -1,8 +1,9 @@
 // listmerge.hip -- the union stage of cw_merge_lists (s/merge-trees,
 // shared.cljc:300-314; a bulk s/insert, :151-184; CausalList's causal-merge).
 // Included by causeweave.hip after mapmerge.hip: it uses the front end's rank
-// directory (fr_rank), the look-back words of mappack.hip and the general
-// route's kernels (k_merge_concat, k_merge_dedup).
+// directory (fr_rank), the general route's kernels (k_merge_concat,
+// k_merge_dedup) and mapmerge.hip's union scaffold (union_sort_dedup,
+// fused_union_tail).
 //
 // Per document the two replicas' node bags are united by id: a repeated id with
 // the same body (cause, kind, value token) is kept once (the copy with the
@@ -23,8 +24,8 @@
 //      rank; popcount(A) < na or popcount(B) < nb is an id repeated inside one
 //      side;
 //   3. m is published at once; the document's first merged position comes
-//      from a decoupled look-back over the documents (epoch-tagged words as
-//      k_map_union's, own buffer and epoch);
+//      from a decoupled look-back over the documents (lookback.h; the stage's
+//      own words and epochs);
 //   4. the merged ids are written straight from plane A | B (a group's set
 //      bits are its ids, ranked from its count word on).  The other outputs
 //      are placed in LDS first: plane A is done with, and its place plus 64 KiB
@@ -160,40 +161,14 @@ __global__ __launch_bounds__(LU_NT) void k_list_union(LuSide sa, LuSide sb, uint
   const bool bail = any_far || repeat;  // (uniform: the general route takes the call)
   if (bail) tot = 0;
   // 3. publish this document's merged count, then sum the predecessors' (one wave)
-  const unsigned long long ep = (unsigned long long)epoch << LB_EPOCH;
   if (tid == 0) {
-    const unsigned long long w = (d == 0 ? LB_INC : LB_AGG) | ep | tot;
-    __hip_atomic_store(lb + d, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    lb_publish(lb, d, epoch, tot);
     if (bail) atomicOr(&ctl[0], any_far ? LU_CTL_FAR : LU_CTL_REPEAT);
   }
   if (bail) return;  // (the successors look past this word; the host discards the call)
   if (tid < 64) {
-    uint32_t base = 0;
-    if (d > 0) {
-      for (int64_t q0 = (int64_t)d - 1;;) {
-        const int64_t q = q0 - lane;  // lane 0 = the nearest predecessor
-        unsigned long long v = q >= 0 ? __hip_atomic_load(lb + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                      : (LB_INC | ep);
-        if (((v >> LB_EPOCH) & 0xFFFFull) != epoch) v = 0;  // an earlier call's word
-        const uint64_t inc = __ballot((v >> 62) == 2), none = __ballot((v >> 62) == 0);
-        const uint32_t first = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive
-        const uint64_t need = first >= 63 ? ~0ull : ((2ull << first) - 1);
-        if (none & need) {  // a document in this window has not counted yet
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        uint32_t x = lane <= first ? (uint32_t)v : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        base += x;
-        if (first < 64) break;
-        q0 -= 64;
-      }
-      if (lane == 0)
-        __hip_atomic_store(lb + d, LB_INC | ep | (unsigned long long)(base + tot), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) *s_base = base;
+    const uint32_t base = lb_exclusive(lb, d, epoch, tot);
+    if (tid == 0) *s_base = base;
   }
   __syncthreads();  // (also: plane A | B is complete)
   const uint32_t base = *s_base;
@@ -330,61 +305,40 @@ int list_union_fused(cw_ctx *c, LuHost &h, uint64_t *mo, const uint64_t **dmo_ou
   auto &lm = c->lmerge;
   const uint64_t D = h.D;
   if (!lm.fits || LU_LDS > c->lds_max) return 1;
-  unsigned long long *lb = scratch_t<unsigned long long>(c, "lm_lb", D);
   uint32_t *ctl = scratch_t<uint32_t>(c, "lm_ctl", 4);
   uint64_t *dmo = scratch_t<uint64_t>(c, "lm_moff", D + 1);
-  if (!lb || !ctl || !dmo) return fail(c, "out of device memory (list merge)");
-  // a new epoch per call; the words are cleared only when the epoch wraps or
-  // the buffer was (re)allocated or holds fewer documents than this call has
-  if (++lm.epoch >= 0xFFFF || lb != lm.lb || D > lm.lb_docs) {
-    HIPCHK(c, hipMemsetAsync(lb, 0, (size_t)D * 8, c->stream));
-    lm.epoch = 1;
-    lm.lb = lb;
-    lm.lb_docs = (uint32_t)D;
-  }
+  if (!ctl || !dmo) return fail(c, "out of device memory (list merge)");
+  uint32_t epoch;
+  unsigned long long *lb = lookback_words(c, lm.lb, "lm_lb", (uint32_t)D, 1, &epoch);
+  if (!lb) return -1;
   HIPCHK(c, hipMemsetAsync(ctl, 0, 16, c->stream));
   const LuOut out{h.mid, h.mca, h.mkd, h.msrc, dmo, h.mst};
   const uint64_t NC = h.Na + h.Nb;
-  size_t stat_idx = (size_t)-1;
+  size_t rec = NO_REC;
   {
     // 25 B per input node here; 21 B per merged node join once the count is known
-    Launch L(c, "list_union", (double)NC * 25);
+    Launch L(c, "list_union", (double)NC * 25, nullptr, &rec);
     hipLaunchKernelGGL(k_list_union, dim3((uint32_t)D), dim3(LU_NT), LU_LDS, c->stream, h.a, h.b,
-                       (uint32_t)D, lb, lm.epoch, out, ctl);
-    if (L.a) stat_idx = c->pending.size();  // (its record is pushed when L goes out of scope)
+                       (uint32_t)D, lb, epoch, out, ctl);
   }
   if (check_launch(c, "list_union")) return -1;
-  // the one device-to-host copy of the stage: the merged offsets (and the flag)
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(mo, dmo, (D + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pin_small[0]) {  // ids past the planes, or repeated inside one side
-    if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes = 0;
-    return 1;
-  }
-  if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes += (double)mo[D] * 21;
-  *dmo_out = dmo;
-  return 0;
+  // (1: ids past the planes, or repeated inside one side)
+  const int rc = fused_union_tail(c, rec, ctl, dmo, mo, D, 21);
+  if (rc == 0) *dmo_out = dmo;
+  return rc;
 }
 
-// The general route: concatenation, segmented sort by id, two dedup passes
-// around a host scan of the counts.  The merged offsets: `mo` (host) and
-// *dmo_out (device u32[D+1]).
+// The general route: concatenation, then union_sort_dedup.  The merged
+// offsets: `mo` (host) and *dmo_out (device u32[D+1]).
 int list_union_general(cw_ctx *c, LuHost &h, uint64_t *mo, const uint32_t **dmo_out) {
   const uint64_t D = h.D, NC = h.Na + h.Nb;
-  const size_t NCs = std::max<uint64_t>(NC, 1);
-  uint32_t *dmo = scratch_t<uint32_t>(c, "g_moff", D + 1), *mcnt = scratch_t<uint32_t>(c, "g_mcnt", D + 1);
-  uint64_t *cid = scratch_t<uint64_t>(c, "g_cid", NCs), *cca = scratch_t<uint64_t>(c, "g_cca", NCs),
-           *cva = scratch_t<uint64_t>(c, "g_cva", NCs);
-  uint8_t *ckd = scratch_t<uint8_t>(c, "g_ckd", NCs);
-  uint64_t *uskA = scratch_t<uint64_t>(c, "g_skA", NCs), *uskB = scratch_t<uint64_t>(c, "g_skB", NCs);
-  uint32_t *usvA = scratch_t<uint32_t>(c, "g_svA", NCs), *usvB = scratch_t<uint32_t>(c, "g_svB", NCs);
-  if (!dmo || !mcnt || !cid || !cca || !cva || !ckd || !uskA || !uskB || !usvA || !usvB)
-    return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
+  uint64_t *cid = scratch_t<uint64_t>(c, "g_cid", NC), *cca = scratch_t<uint64_t>(c, "g_cca", NC),
+           *cva = scratch_t<uint64_t>(c, "g_cva", NC);
+  uint8_t *ckd = scratch_t<uint8_t>(c, "g_ckd", NC);
+  if (!cid || !cca || !cva || !ckd) return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
   std::vector<uint64_t> cap(D + 1);
   for (uint64_t d = 0; d <= D; d++) cap[d] = h.ao[d] + h.bo[d];
-  // 1. union: a then b per document, in capacity slots
+  // union: a then b per document, in capacity slots
   {
     Launch L(c, "merge_concat", (double)NC * 50);
     hipLaunchKernelGGL(k_merge_concat, dim3((uint32_t)D), dim3(256), 0, c->stream, h.a.id, h.a.cause,
@@ -392,39 +346,10 @@ int list_union_general(cw_ctx *c, LuHost &h, uint64_t *mo, const uint32_t **dmo_
                        h.coff, cid, cca, ckd, cva);
   }
   if (check_launch(c, "merge_concat")) return -1;
-  // 2. id order per capacity slot (the general segmented radix sort)
-  if (ensure_tables(c, D, cap.data())) return -1;
-  if (h.key_bits == 0 && find_key_bits(c, cid, (uint32_t)NC, &h.key_bits)) return -1;
-  uint64_t *skey;
-  uint32_t *sval;
-  if (radix_sort<uint64_t>(c, "m_idsort", cid, nullptr, uskA, usvA, uskB, usvB, h.key_bits, 0,
-                           (uint32_t)NC, &skey, &sval))
-    return -1;
-  // 3. dedup: count, offsets, write
-  {
-    Launch L(c, "merge_count", (double)NC * 12);
-    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval,
-                       cca, ckd, cva, h.coff, 0, mcnt, dmo, h.mid, h.mca, h.mkd, h.msrc, h.mst);
-  }
-  if (check_launch(c, "merge_count")) return -1;
-  std::vector<uint32_t> h_cnt(D), h_mo(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
-  mo[0] = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    mo[d + 1] = mo[d] + h_cnt[d];
-    h_mo[d] = (uint32_t)mo[d];
-  }
-  h_mo[D] = (uint32_t)mo[D];
-  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  {
-    Launch L(c, "merge_write", (double)NC * 12 + (double)mo[D] * 21);
-    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval,
-                       cca, ckd, cva, h.coff, 1, mcnt, dmo, h.mid, h.mca, h.mkd, h.msrc, h.mst);
-  }
-  if (check_launch(c, "merge_write")) return -1;
-  *dmo_out = dmo;
-  return 0;
+  const UnionNames nm{"g_skA",  "g_skB",    "g_svA",       "g_svB",      "g_mcnt",
+                      "g_moff", "m_idsort", "merge_count", "merge_write"};
+  return union_sort_dedup(c, nm, UnionCat{cid, cca, cva, ckd, h.coff, cap.data()}, D, NC, &h.key_bits, mo,
+                          dmo_out, h.mid, h.mca, h.mkd, h.msrc, h.mst);
 }
 
 }  // namespace

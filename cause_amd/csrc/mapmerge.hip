@@ -1,6 +1,6 @@
 // mapmerge.hip -- the union stage of cw_merge_maps (CausalMap causal-merge,
 // map.cljc:248-249 = s/merge-trees, shared.cljc:300-314, with the map weave).
-// Included by causeweave.hip after mappack.hip (mp_sort, the look-back words)
+// Included by causeweave.hip after mappack.hip (mp_sort, the pack table)
 // and the list merge's kernels (k_merge_dedup), which the general route reuses.
 //
 // Per collection the two replicas' node bags are united by id: a repeated id
@@ -23,7 +23,7 @@
 //   4. a block scan of the keep flags: merged positions and per-collection
 //      merged starts;
 //   5. the pack's first merged node by a decoupled look-back over the packs
-//      (epoch-tagged words as k_map_pack's, own buffer and epoch);
+//      (lookback.h; the stage's own words and epochs);
 //   6. merged id / cause / cause_is_id / kind / source, the merged offsets
 //      (device u64[D+1]) and the union status at their final places.
 // LDS at PK = 2048: sorted keys, causes, values 3 x 16 KiB, sort values /
@@ -195,39 +195,10 @@ __global__ __launch_bounds__(NT) void k_map_union(MuSide sa, MuSide sb,
     if (wb_elem<IT>(u) < len) POS[wb_elem<IT>(u)] = (uint16_t)pos[u];
   }
   // 5. publish this pack's merged count, then sum the predecessors' (one wave)
-  const unsigned long long ep = (unsigned long long)epoch << LB_EPOCH;
-  if (tid == 0) {
-    const unsigned long long w = (pk == 0 ? LB_INC : LB_AGG) | ep | tot;
-    __hip_atomic_store(lb + pk, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid == 0) lb_publish(lb, pk, epoch, tot);
   if (tid < 64) {
-    const uint32_t lane = tid;
-    uint32_t base = 0;
-    if (pk > 0) {
-      for (int64_t q0 = (int64_t)pk - 1;;) {
-        const int64_t q = q0 - lane;  // lane 0 = the nearest predecessor
-        unsigned long long v = q >= 0 ? __hip_atomic_load(lb + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                                      : (LB_INC | ep);
-        if (((v >> LB_EPOCH) & 0xFFFFull) != epoch) v = 0;  // an earlier call's word
-        const uint64_t inc = __ballot((v >> 62) == 2), none = __ballot((v >> 62) == 0);
-        const uint32_t first = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive
-        const uint64_t need = first >= 63 ? ~0ull : ((2ull << first) - 1);
-        if (none & need) {  // a pack in this window has not counted yet
-          __builtin_amdgcn_s_sleep(1);
-          continue;
-        }
-        uint32_t x = lane <= first ? (uint32_t)v : 0u;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        base += x;
-        if (first < 64) break;
-        q0 -= 64;
-      }
-      if (lane == 0)
-        __hip_atomic_store(lb + pk, LB_INC | ep | (unsigned long long)(base + tot), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (lane == 0) s_base = base;
+    const uint32_t base = lb_exclusive(lb, pk, epoch, tot);
+    if (tid == 0) s_base = base;
   }
   __syncthreads();
   const uint32_t base = s_base;
@@ -304,6 +275,79 @@ __global__ __launch_bounds__(256) void k_mm_finish(const uint64_t *__restrict__ 
 
 namespace {
 
+// ---- the union scaffold shared with listmerge.hip ----
+
+// After a fused union kernel (k_map_union, k_list_union): the stage's one
+// device-to-host copy -- the control word and the merged offsets (device
+// u64[D+1] -> mo) in one wait.  Returns 1 when the kernel handed the call to
+// the general route, else 0; the launch's profiling record `rec` gets its
+// bytes: none then, else out_bytes more per merged node.
+int fused_union_tail(cw_ctx *c, size_t rec, const uint32_t *ctl, const uint64_t *dmo, uint64_t *mo,
+                     uint64_t D, double out_bytes) {
+  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(mo, dmo, (D + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const bool bail = c->pin_small[0] != 0;
+  if (rec < c->pending.size()) c->pending[rec].bytes = bail ? 0 : c->pending[rec].bytes + (double)mo[D] * out_bytes;
+  return bail;
+}
+
+struct UnionNames {  // a caller's scratch and kernel stat names
+  const char *skA, *skB, *svA, *svB, *cnt, *moff, *idsort, *count, *write;
+};
+struct UnionCat {  // the two sides in capacity slots: a's nodes then b's per document
+  const uint64_t *id, *cause, *val;
+  const uint8_t *kind;
+  const uint32_t *coff;  // device [D+1]
+  const uint64_t *cap;   // the same on the host
+};
+
+// The general route after the concatenation: id order per capacity slot (the
+// segmented radix sort), k_merge_dedup's count pass, a host scan of the counts,
+// its write pass.  The merged offsets: mo (host) and *dmo_out (device u32[D+1]);
+// *key_bits == 0: found here.
+int union_sort_dedup(cw_ctx *c, const UnionNames &nm, const UnionCat &cat, uint64_t D, uint64_t NC,
+                     uint32_t *key_bits, uint64_t *mo, const uint32_t **dmo_out, uint64_t *mid,
+                     uint64_t *mca, uint8_t *mkd, uint32_t *msrc, uint32_t *mst) {
+  uint32_t *dmo = scratch_t<uint32_t>(c, nm.moff, D + 1), *mcnt = scratch_t<uint32_t>(c, nm.cnt, D + 1);
+  uint64_t *skA = scratch_t<uint64_t>(c, nm.skA, NC), *skB = scratch_t<uint64_t>(c, nm.skB, NC);
+  uint32_t *svA = scratch_t<uint32_t>(c, nm.svA, NC), *svB = scratch_t<uint32_t>(c, nm.svB, NC);
+  if (!dmo || !mcnt || !skA || !skB || !svA || !svB)
+    return fail(c, "out of device memory (merge, N=%llu)", (unsigned long long)NC);
+  if (ensure_tables(c, D, cat.cap)) return -1;
+  if (*key_bits == 0 && find_key_bits(c, cat.id, (uint32_t)NC, key_bits)) return -1;
+  uint64_t *skey;
+  uint32_t *sval;
+  if (radix_sort<uint64_t>(c, nm.idsort, cat.id, nullptr, skA, svA, skB, svB, *key_bits, 0, (uint32_t)NC,
+                           &skey, &sval))
+    return -1;
+  auto dedup = [&](const char *stat, int pass, double bytes) {
+    {
+      Launch L(c, stat, bytes);
+      hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval,
+                         cat.cause, cat.kind, cat.val, cat.coff, pass, mcnt, dmo, mid, mca, mkd, msrc, mst);
+    }
+    return check_launch(c, stat);
+  };
+  if (dedup(nm.count, 0, (double)NC * 12)) return -1;
+  std::vector<uint32_t> h_cnt(D), h_mo(D + 1);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
+  mo[0] = 0;
+  for (uint64_t d = 0; d < D; d++) {
+    mo[d + 1] = mo[d] + h_cnt[d];
+    h_mo[d] = (uint32_t)mo[d];
+  }
+  h_mo[D] = (uint32_t)mo[D];
+  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  if (dedup(nm.write, 1, (double)NC * 12 + (double)mo[D] * 21)) return -1;
+  *dmo_out = dmo;
+  return 0;
+}
+
+// ---- cw_merge_maps ----
+
 struct MuHost {  // what merge_maps_impl hands the union stage (device pointers)
   uint64_t D, Na, Nb;
   const uint64_t *ao, *bo;  // host offsets
@@ -322,22 +366,14 @@ int map_union_fused(cw_ctx *c, MuHost &h, uint64_t *mo) {
                     memcmp(mm.ao.data(), ao, (D + 1) * 8) == 0 &&
                     memcmp(mm.bo.data(), bo, (D + 1) * 8) == 0;
   if (!same) {  // pack table, cached while both layouts repeat
-    uint64_t mx = 0;
-    for (uint64_t d = 0; d < D; d++) mx = std::max(mx, (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]));
     mm.ao.assign(ao, ao + D + 1);
     mm.bo.assign(bo, bo + D + 1);
-    mm.ok = mx <= MPK;
-    mm.pk = mx <= 512 ? 512u : mx <= 1024 ? 1024u : MPK;
-    mm.doc0.clear();
-    mm.dmax = 1;
+    uint64_t mx = 0;
+    for (uint64_t d = 0; d < D; d++) mx = std::max(mx, (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]));
+    mm.pk = map_pack_size(mx);
+    mm.ok = mx <= MPK && pack_runs(D, ao, bo, mm.pk, MU_MAXCOLL, mm.doc0, &mm.dmax);
+    mm.dmax = std::max(mm.dmax, 1u);
     if (mm.ok) {
-      for (uint64_t d = 0; d < D;) {
-        const uint64_t s = d;
-        while (d < D && (ao[d + 1] - ao[s]) + (bo[d + 1] - bo[s]) <= mm.pk && d - s < MU_MAXCOLL) d++;
-        mm.doc0.push_back((uint32_t)s);
-        mm.dmax = std::max<uint32_t>(mm.dmax, (uint32_t)(d - s));
-      }
-      mm.doc0.push_back((uint32_t)D);
       const size_t P1 = mm.doc0.size();
       std::vector<uint64_t> pa(P1), pb(P1);
       for (size_t k = 0; k < P1; k++) {
@@ -362,18 +398,12 @@ int map_union_fused(cw_ctx *c, MuHost &h, uint64_t *mo) {
   if (!mm.ok) return 1;
   const uint32_t P = (uint32_t)mm.doc0.size() - 1;
   const uint64_t NC = h.Na + h.Nb;
-  unsigned long long *lb = scratch_t<unsigned long long>(c, "mm_lb", P);
   uint32_t *ctl = scratch_t<uint32_t>(c, "mm_ctl", 4);
   uint64_t *dmo = scratch_t<uint64_t>(c, "mm_moff", D + 1);
-  if (!lb || !ctl || !dmo) return fail(c, "out of device memory (map merge)");
-  // a new epoch per call; the words are cleared only when the epoch wraps or
-  // the buffer was (re)allocated or holds fewer packs than this call has
-  if (++mm.epoch >= 0xFFFF || lb != mm.lb || P > mm.lb_packs) {
-    HIPCHK(c, hipMemsetAsync(lb, 0, (size_t)P * 8, c->stream));
-    mm.epoch = 1;
-    mm.lb = lb;
-    mm.lb_packs = P;
-  }
+  if (!ctl || !dmo) return fail(c, "out of device memory (map merge)");
+  uint32_t epoch;
+  unsigned long long *lb = lookback_words(c, mm.lb, "mm_lb", P, 1, &epoch);
+  if (!lb) return -1;
   HIPCHK(c, hipMemsetAsync(ctl, 0, 16, c->stream));
   h.a.off = (const uint64_t *)c->bufs["mm_aoff"].p;
   h.b.off = (const uint64_t *)c->bufs["mm_boff"].p;
@@ -382,31 +412,15 @@ int map_union_fused(cw_ctx *c, MuHost &h, uint64_t *mo) {
   h.out.off = dmo;
   const uint32_t *dp = (const uint32_t *)c->bufs["mm_doc0"].p;
   const size_t dyn = (size_t)mm.dmax * 4 + (size_t)(mm.dmax + 1) * 4;
-  size_t stat_idx = (size_t)-1;
+  size_t rec = NO_REC;
   {
     // 26 B per input node here; 22 B per merged node join once the count is known
-    Launch L(c, "map_union", (double)NC * 26);
-#define CW_MAP_UNION_LAUNCH(PK_, NT_)                                                            \
-  hipLaunchKernelGGL((k_map_union<PK_, NT_>), dim3(P), dim3(NT_), dyn, c->stream, h.a, h.b, dp, P, \
-                     (uint32_t)D, lb, mm.epoch, mm.dmax, h.out, ctl)
-    if (mm.pk == 512) CW_MAP_UNION_LAUNCH(512, 128);
-    else if (mm.pk == 1024) CW_MAP_UNION_LAUNCH(1024, 256);
-    else CW_MAP_UNION_LAUNCH(2048, 512);
-#undef CW_MAP_UNION_LAUNCH
-    if (L.a) stat_idx = c->pending.size();  // (its record is pushed when L goes out of scope)
+    Launch L(c, "map_union", (double)NC * 26, nullptr, &rec);
+    CW_PK_LAUNCH(k_map_union, mm.pk, P, dyn, c->stream, h.a, h.b, dp, P, (uint32_t)D, lb, epoch, mm.dmax,
+                 h.out, ctl);
   }
   if (check_launch(c, "map_union")) return -1;
-  // the one device-to-host copy of the stage: the merged offsets (and the flag)
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(mo, dmo, (D + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pin_small[0]) {  // a pack's sort keys need more than 63 bits
-    if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes = 0;
-    return 1;
-  }
-  if (stat_idx < c->pending.size()) c->pending[stat_idx].bytes += (double)mo[D] * 22;
-  return 0;
+  return fused_union_tail(c, rec, ctl, dmo, mo, D, 22);  // (1: a pack's sort keys need more than 63 bits)
 }
 
 // The general route: the list merge's scheme with map bodies.
@@ -420,14 +434,11 @@ int map_union_general(cw_ctx *c, MuHost &h, uint64_t *mo) {
     h_co[d] = (uint32_t)cap[d];
   }
   uint64_t *dao = scratch_t<uint64_t>(c, "mm_aoff", D + 1), *dbo = scratch_t<uint64_t>(c, "mm_boff", D + 1);
-  uint32_t *dco = scratch_t<uint32_t>(c, "mm_coff", D + 1), *dmo = scratch_t<uint32_t>(c, "mm_moff32", D + 1);
+  uint32_t *dco = scratch_t<uint32_t>(c, "mm_coff", D + 1);
   uint64_t *cid = scratch_t<uint64_t>(c, "mm_cid", NC), *cca = scratch_t<uint64_t>(c, "mm_cca", NC),
            *cva = scratch_t<uint64_t>(c, "mm_cva", NC);
   uint8_t *ckd = scratch_t<uint8_t>(c, "mm_ckd", NC);
-  uint32_t *mcnt = scratch_t<uint32_t>(c, "mm_cnt", D + 1);
-  uint64_t *skA = scratch_t<uint64_t>(c, "mm_skA", NC), *skB = scratch_t<uint64_t>(c, "mm_skB", NC);
-  uint32_t *svA = scratch_t<uint32_t>(c, "mm_svA", NC), *svB = scratch_t<uint32_t>(c, "mm_svB", NC);
-  if (!dao || !dbo || !dco || !dmo || !cid || !cca || !cva || !ckd || !mcnt || !skA || !skB || !svA || !svB)
+  if (!dao || !dbo || !dco || !cid || !cca || !cva || !ckd)
     return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
   c->mmerge.ao.clear();  // (mm_aoff / mm_boff are rewritten: the fused route's cache is void)
   c->mmerge.bo.clear();
@@ -444,48 +455,21 @@ int map_union_general(cw_ctx *c, MuHost &h, uint64_t *mo) {
                        ckd, cva);
   }
   if (check_launch(c, "mm_concat")) return -1;
-  // 2. id order per capacity slot (the general segmented radix sort)
-  if (ensure_tables(c, D, cap.data())) return -1;
+  // 2. id sort and dedup (scratch names of its own: weave_maps_impl reuses the lists')
+  const UnionNames nm{"mm_skA",    "mm_skB",    "mm_svA",   "mm_svB",  "mm_cnt",
+                      "mm_moff32", "mm_idsort", "mm_count", "mm_write"};
+  const uint32_t *dmo;
   uint32_t key_bits = h.key_bits;
-  if (key_bits == 0 && find_key_bits(c, cid, (uint32_t)NC, &key_bits)) return -1;
-  uint64_t *skey;
-  uint32_t *sval;
-  if (radix_sort<uint64_t>(c, "mm_idsort", cid, nullptr, skA, svA, skB, svB, key_bits, 0, (uint32_t)NC,
-                           &skey, &sval))
+  if (union_sort_dedup(c, nm, UnionCat{cid, cca, cva, ckd, dco, cap.data()}, D, NC, &key_bits, mo, &dmo,
+                       h.out.id, h.out.cause, h.out.kind, h.out.src, h.out.status))
     return -1;
-  // 3. dedup: count, host offsets, write (the list merge's kernel)
-  {
-    Launch L(c, "mm_count", (double)NC * 12);
-    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval, cca,
-                       ckd, cva, dco, 0, mcnt, dmo, h.out.id, h.out.cause, h.out.kind, h.out.src,
-                       h.out.status);
-  }
-  if (check_launch(c, "mm_count")) return -1;
-  std::vector<uint32_t> h_cnt(D), h_mo(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
-  mo[0] = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    mo[d + 1] = mo[d] + h_cnt[d];
-    h_mo[d] = (uint32_t)mo[d];
-  }
-  h_mo[D] = (uint32_t)mo[D];
-  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  {
-    Launch L(c, "mm_write", (double)NC * 12 + (double)mo[D] * 21);
-    hipLaunchKernelGGL((k_merge_dedup<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, skey, sval, cca,
-                       ckd, cva, dco, 1, mcnt, dmo, h.out.id, h.out.cause, h.out.kind, h.out.src,
-                       h.out.status);
-  }
-  if (check_launch(c, "mm_write")) return -1;
-  // 4. kind / cause_is_id apart again, and the orphan search
+  // 3. kind / cause_is_id apart again, and the orphan search
   {
     Launch L(c, "mm_finish", (double)mo[D] * 19);
     hipLaunchKernelGGL(k_mm_finish, dim3((uint32_t)D), dim3(256), 0, c->stream, h.out.id, h.out.cause, dmo,
                        h.out.kind, h.out.cis, h.out.status);
   }
-  if (check_launch(c, "mm_finish")) return -1;
-  return 0;
+  return check_launch(c, "mm_finish");
 }
 
 }  // namespace

@@ -19,8 +19,8 @@
 //      length up to the pack;
 //   5. active-node per key weave (first rendered value, ::blank behind a hide).
 // Key weaves are numbered across the batch with a decoupled look-back over the
-// packs (a pack publishes its count, then sums its predecessors'), so every
-// output goes straight to its final place: one pass over the inputs, one over
+// packs (lookback.h: a pack publishes its count, then sums its predecessors'),
+// so every output goes straight to its final place: one pass over the inputs, one over
 // the outputs, instead of the eleven kernels and three host readbacks of the
 // general map path (kept for collections of more than MPK nodes).
 //
@@ -35,11 +35,6 @@ constexpr uint16_t MP_ROOT = 0xFFFFu;          // cause-in-weave = the key weave
 constexpr uint16_t MP_CHAIN = 0xFFFEu;         // appended after the previous node
 constexpr uint16_t MP_ROOT_ID = 0xFFFDu;       // caused by the root id [0 "0" 0] (not a node)
 constexpr uint16_t ML_ABSENT = 0xFFFFu;        // literal fold: the cause is not in the key weave
-constexpr unsigned long long LB_AGG = 1ull << 62, LB_INC = 2ull << 62;
-// look-back word: flags (2 bits) | the call's epoch (16 bits, LB_EPOCH) | count:
-// a word of an earlier call reads as "not published yet", so the words need
-// no clearing before each call (cw_ctx::mpack.epoch; cleared when it wraps)
-constexpr uint32_t LB_EPOCH = 46;
 
 // Stable LDS radix sort of the pack's wave-blocked items by the low `bits` of
 // ck (carrying val), 6 bits per sub-pass.  On return item u holds the element
@@ -422,11 +417,7 @@ __global__ __launch_bounds__(NT) void k_map_pack(
   stamp(2);
   // 4. publish this pack's number of key weaves (its prefix comes after the
   // weave below, so the wait for earlier packs overlaps this pack's work)
-  const unsigned long long ep = (unsigned long long)epoch << LB_EPOCH;
-  if (tid == 0) {
-    const unsigned long long w = (pk == 0 ? LB_INC : LB_AGG) | ep | nseg;
-    __hip_atomic_store(lb + pk, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tid == 0) lb_publish(lb, pk, epoch, nseg);
 
   // 5. each key weave's list weave: member 0 the root, members 1..m in id order
   uint32_t mst[IT], mm[IT], mr[IT], me[IT];
@@ -673,52 +664,12 @@ __global__ __launch_bounds__(NT) void k_map_pack(
   }
   stamp(4);
   // 7. this pack's first key weave number: decoupled look-back over the packs,
-  // one wave reading LBW windows of 64 predecessors per round trip (earlier
-  // packs are dispatched first and publish their counts before weaving, so the
-  // wait always ends).  The resident packs reach their look-backs together, so
-  // the nearest inclusive prefix is typically a whole residency (~500 packs)
-  // back: one window per round trip cost ~8 L2 round trips (20k clocks).
+  // one wave, a window of 64 predecessors per round trip.  The resident packs
+  // reach their look-backs together, so the nearest inclusive prefix is
+  // typically a whole residency (~500 packs) back: ~8 L2 round trips (20k clocks).
   if (tid < 64) {
-    constexpr uint32_t LBW = 1, lbw = 1;  // (four windows a round trip lost in round 3)
-    const uint32_t lane = tid;
-    uint32_t base = 0;
-    if (pk > 0) {
-      for (int64_t q0 = (int64_t)pk - 1;;) {
-        unsigned long long v[LBW];
-#pragma unroll
-        for (uint32_t k = 0; k < LBW; k++) {
-          const int64_t q = q0 - 64 * (int64_t)k - lane;  // lane 0 of window 0 = the nearest
-          v[k] = !(q >= 0 && k < lbw) ? (k < lbw ? LB_INC | ep : 0ull)
-                 : __hip_atomic_load(lb + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          if (((v[k] >> LB_EPOCH) & 0xFFFFull) != epoch) v[k] = 0;  // an earlier call's word
-        }
-        bool done = false, retry = false;  // (wave-uniform: ballots)
-#pragma unroll
-        for (uint32_t k = 0; k < LBW; k++) {
-          if (done || retry || k >= lbw) continue;
-          const uint64_t inc = __ballot((v[k] >> 62) == 2), none = __ballot((v[k] >> 62) == 0);
-          const uint32_t first = inc ? (uint32_t)__builtin_ctzll(inc) : 64u;  // nearest inclusive
-          const uint64_t need = first >= 63 ? ~0ull : ((2ull << first) - 1);
-          if (none & need) {  // a pack in this window has not counted its key weaves yet
-            retry = true;
-            continue;
-          }
-          uint32_t x = lane <= first ? (uint32_t)v[k] : 0u;
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-          base += x;
-          if (first < 64) done = true;
-          else q0 -= 64;
-        }
-        if (done) break;
-        if (retry) __builtin_amdgcn_s_sleep(1);
-      }
-      if (lane == 0)
-      {
-        __hip_atomic_store(lb + pk, LB_INC | ep | (base + nseg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-    if (lane == 0) {
+    const uint32_t base = lb_exclusive(lb, pk, epoch, nseg);
+    if (tid == 0) {
       s_base = base;
       if ((uint64_t)base + nseg > cap_segs) atomicOr(&ctl[1], 1u);
       if (pk == P - 1) {  // the batch's number of key weaves, and the end offset
@@ -757,6 +708,20 @@ __global__ __launch_bounds__(NT) void k_map_pack(
 
 namespace {
 
+// Pack size: the smallest of 512 / 1024 / 2048 nodes that holds the largest
+// collection -- smaller packs are more workgroups a CU with cheaper barriers
+// (config 4: 2048 nodes 3.77 ms, 1024 3.26, 512 3.15; 256 nodes / one wave:
+// 3.95).  The kernels' instances are <PK, PK / 4 threads>.
+uint32_t map_pack_size(uint64_t largest) { return largest <= 512 ? 512u : largest <= 1024 ? 1024u : MPK; }
+
+// One launch of a kernel template <PK, NT> at the pack size pk.
+#define CW_PK_LAUNCH(KERN, pk, P, dyn, stream, ...)                                              \
+  do {                                                                                           \
+    if ((pk) == 512) hipLaunchKernelGGL((KERN<512, 128>), dim3(P), dim3(128), dyn, stream, __VA_ARGS__);        \
+    else if ((pk) == 1024) hipLaunchKernelGGL((KERN<1024, 256>), dim3(P), dim3(256), dyn, stream, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERN<2048, 512>), dim3(P), dim3(512), dyn, stream, __VA_ARGS__);                   \
+  } while (0)
+
 // cw_weave_maps through k_map_pack: every collection <= MPK nodes and every
 // pack's sort keys fit 63 bits (each pack finds its own key widths: no
 // reduction over the batch and no readback before the kernel).  Returns 1 when it does not apply (the caller takes
@@ -770,32 +735,13 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
   const uint32_t N = (uint32_t)off[D];
   // pack table, cached while the collection layout repeats
   auto &pc = c->mpack;
-  // pack size: the smallest of 512 / 1024 / 2048
-  // nodes that holds the largest collection -- smaller packs are more
-  // workgroups a CU with cheaper barriers (config 4: 2048 nodes 3.77 ms,
-  // 1024 3.26, 512 3.15; 256 nodes / one wave: 3.95)
-  const uint64_t mc = pc.maxcoll;
-  const uint32_t PKN = mc <= 512 ? 512u : mc <= 1024 ? 1024u : MPK;
+  const uint32_t PKN = map_pack_size(pc.maxcoll);
   if (!(pc.pk == PKN && pc.same)) {
     pc.off.assign(off, off + D + 1);
     pc.pk = PKN;
-    pc.doc0.clear();
-    pc.ok = true;
-    uint32_t dmax = 1;
-    pc.dmax = 1;
-    for (uint64_t d = 0; d < D;) {
-      const uint64_t a = d;
-      while (d < D && off[d + 1] - off[a] <= PKN) d++;
-      if (d == a) {  // a collection of more than MPK nodes
-        pc.ok = false;
-        break;
-      }
-      pc.doc0.push_back((uint32_t)a);
-      dmax = std::max<uint32_t>(dmax, (uint32_t)(d - a));
-    }
-    pc.doc0.push_back((uint32_t)D);
-    pc.dbits = ceil_log2(dmax);
-    pc.dmax = dmax;
+    pc.ok = pack_runs(D, off, nullptr, PKN, D, pc.doc0, &pc.dmax);  // (false: a collection of more than MPK nodes)
+    pc.dmax = std::max(pc.dmax, 1u);
+    pc.dbits = ceil_log2(pc.dmax);
     if (pc.ok) {
       uint32_t *dp = scratch_t<uint32_t>(c, "mp_doc0", pc.doc0.size());
       uint64_t *dof = scratch_t<uint64_t>(c, "mp_off", D + 1);
@@ -813,9 +759,8 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
   if (!pc.ok) return 1;
   const uint32_t P = (uint32_t)pc.doc0.size() - 1;
   const uint64_t cap = res->cap_segs;
-  unsigned long long *lb = scratch_t<unsigned long long>(c, "mp_lb", P);
   uint32_t *ctl = scratch_t<uint32_t>(c, "mp_ctl", 4);
-  if (!lb || !ctl) return fail(c, "out of device memory (map packs)");
+  if (!ctl) return fail(c, "out of device memory (map packs)");
   // outputs: the caller's arrays (device memory) or staging (host memory)
   uint64_t *so = res->seg_offsets, *sk = res->seg_key;
   uint32_t *sc = res->seg_coll, *sp = res->seg_perm, *st = res->status;
@@ -831,30 +776,18 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
   }
   unsigned long long *tprof = nullptr;
   if (c->tree_prof && alloc_stamps(c, "mp_tprof", P, 8, &tprof)) return -1;
-  // a new epoch per call; the words are cleared only when the epoch wraps or
-  // the buffer was (re)allocated for more packs than it held
-  if (++pc.epoch >= 0xFFFF || lb != pc.lb || P > pc.lb_packs) {
-    HIPCHK(c, hipMemsetAsync(lb, 0, (size_t)P * 8, c->stream));
-    pc.epoch = 1;
-    pc.lb = lb;
-    pc.lb_packs = P;
-  }
+  uint32_t epoch;
+  unsigned long long *lb = lookback_words(c, pc.lb, "mp_lb", P, 1, &epoch);
+  if (!lb) return -1;
   HIPCHK(c, hipMemsetAsync(ctl, 0, 16, c->stream));
   {
     // ids, causes, flags and kinds in; per node seg_perm, per key weave
     // offsets, collection, key, active node out
     Launch L(c, "m_pack", (double)N * (8 + 8 + 1 + 1 + 4) + (double)N * 0.42 * (4 + 8 + 4 + 8 + 8));
-#define CW_MAP_PACK_LAUNCH(PK_, NT_)                                                              \
-  hipLaunchKernelGGL((k_map_pack<PK_, NT_>), dim3(P), dim3(NT_), (size_t)(2 * pc.dmax + 1) * 4,       \
-                     c->stream, id, cause, cis, kind,                                                  \
-                     (const uint64_t *)c->bufs["mp_off"].p, (const uint32_t *)c->bufs["mp_doc0"].p, \
-                     (const uint64_t *)c->bufs["mp_s0"].p,                                             \
-                     P, bt->token_bits, lb, cap, (uint64_t)N, so, sc, sk, sa,                          \
-                     sp, st, ctl, tprof, pc.dmax, pc.epoch)
-    if (pc.pk == 512) CW_MAP_PACK_LAUNCH(512, 128);
-    else if (pc.pk == 1024) CW_MAP_PACK_LAUNCH(1024, 256);
-    else CW_MAP_PACK_LAUNCH(2048, 512);
-#undef CW_MAP_PACK_LAUNCH
+    CW_PK_LAUNCH(k_map_pack, pc.pk, P, (size_t)(2 * pc.dmax + 1) * 4, c->stream, id, cause, cis, kind,
+                 (const uint64_t *)c->bufs["mp_off"].p, (const uint32_t *)c->bufs["mp_doc0"].p,
+                 (const uint64_t *)c->bufs["mp_s0"].p, P, bt->token_bits, lb, cap, (uint64_t)N, so, sc, sk,
+                 sa, sp, st, ctl, tprof, pc.dmax, epoch);
   }
   if (check_launch(c, "map_pack")) return -1;
   if (pc.verify &&

@@ -466,7 +466,42 @@ def test_repeated_and_alternating_calls(weaver, sizes_split):
     same(weaver.merge_lists(oa, ob, LAYOUT), other)
 
 
-# ------------------------------------------------------------------ 9. bad inputs
+# ------------------------------------------------------------------ 9. look-back windows
+def tiny_docs(D, empty_every=0):
+    """D documents of 2 to 5 nodes, 1 to 3 of them a side; every empty_every-th
+    document empty on both sides."""
+    sizes = [0 if empty_every and d % empty_every == empty_every - 1 else 2 + d % 4 for d in range(D)]
+    (a, _), (b, _) = split_batch(*docs_of(sizes, seed=50), np.random.default_rng(D), overlap=0.2)
+    na, nb = np.diff(a[0].astype(np.int64)), np.diff(b[0].astype(np.int64))
+    full = np.array(sizes) > 0
+    assert ((na[full] >= 1) & (na[full] <= 3) & (nb[full] >= 1) & (nb[full] <= 3)).all()
+    assert not na[~full].any() and not nb[~full].any()
+    return a, b
+
+
+@pytest.mark.parametrize("D", [64, 65, 66, 128, 129, 130, 200])
+def test_document_counts_around_the_look_back_window(weaver, D):
+    """k_list_union sums its predecessors' merged counts 64 words at a time: a
+    document with 64 or 128 predecessors ends its look-back exactly on a window's
+    boundary, one with 65 or 129 reads a window of one word."""
+    a, b = tiny_docs(D)
+    res = check(weaver, a, b, LAYOUT)
+    assert not res.weave.status.any()
+
+
+def test_empty_documents_among_the_look_back_words(weaver):
+    """Every tenth of 200 documents is empty on both sides: its word adds 0, and
+    the document after it starts where it does."""
+    a, b = tiny_docs(200, empty_every=10)
+    res = check(weaver, a, b, LAYOUT)
+    moff = res.offsets.astype(np.int64)
+    empty = np.arange(9, 200, 10)
+    np.testing.assert_array_equal(moff[empty + 1], moff[empty])
+    np.testing.assert_array_equal(res.weave.status[empty], abi.STATUS_ROOT)
+    assert not np.delete(res.weave.status, empty).any()
+
+
+# ------------------------------------------------------------------ 10. bad inputs
 def raw_call(weaver, a, b, layout, tweak, memspace=abi.CW_MEM_HOST):
     """cw_merge_lists through the C ABI with one field spoiled by tweak(batch,
     result, a_offsets).  The arrays are host memory; every check this test aims

@@ -229,6 +229,20 @@ def test_packs_filled_exactly(weaver):
         check(weaver, a, b, 3)
 
 
+@pytest.mark.parametrize("colls", [65, 129])
+def test_packs_at_a_look_back_window_boundary(weaver, colls):
+    """Collections of na + nb = 300 are one 512-node pack each: with 65 and 129 of
+    them the last pack of k_map_union has 64 and 128 predecessors: its look-back
+    ends exactly on the boundary of a 64-word window (the first, the second)."""
+    off, *cols = sized([250] * colls, 300)
+    a, b, _, _ = split(off, cols, [50] * colls, np.random.default_rng(colls))
+    tot = np.diff(a[0].astype(np.int64)) + np.diff(b[0].astype(np.int64))
+    assert (tot == 300).all()
+    res, bits = check(weaver, a, b, 3)
+    assert not bits.any()
+    np.testing.assert_array_equal(res.offsets, off)
+
+
 def test_empty_collections_and_empty_batches(weaver):
     off, *cols = sized([4, 7, 0, 5, 0, 0, 9, 3], 70)
     a, b, _, _ = split(off, cols, 0.3, np.random.default_rng(4), only={1: "a", 3: "b", 7: "a"})

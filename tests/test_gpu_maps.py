@@ -115,6 +115,19 @@ def test_config4_shape(weaver):
     assert (res.status == 0).all()
 
 
+@pytest.mark.parametrize("colls", [65, 129])
+def test_packs_at_a_look_back_window_boundary(weaver, colls):
+    """Collections of 300 nodes are one 512-node pack each: with 65 and 129 of
+    them the last pack of k_map_pack has 64 and 128 predecessors: its look-back
+    ends exactly on the boundary of a 64-word window (the first, the second)."""
+    spec = gen.MapSpec(nodes_per_coll=300, n_keys=40, seed=15)
+    _, tb = spec.layout()
+    off, idk, ck, ci, kd = gen.generate_maps(spec, 0, colls, nthreads=4)
+    assert np.all(np.diff(off.astype(np.int64)) == 300)
+    res = check(weaver, off, idk, ck, ci, kd, tb)
+    assert (res.status == 0).all()
+
+
 def test_large_collections_few_keys(weaver):
     # long key weaves: few keys, many writes and id-caused undo/redo per key
     spec = gen.MapSpec(nodes_per_coll=20_000, n_keys=5, zipf_s=0.5, seed=11)
