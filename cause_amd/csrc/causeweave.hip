@@ -4439,7 +4439,7 @@ struct cw_ctx {
   // rank-directory front end (front; front_slot: directory bytes per document,
   // 16-byte groups; front_min_avg: least average document size that takes it)
   uint32_t front = 1, front_slot = 65536, front_min_avg = 1024;
-  uint32_t *pin_small = nullptr;  // pinned 16-byte readback
+  uint32_t *pin_small = nullptr;  // pinned PIN_SMALL_BYTES readback (read_small)
   uint32_t tree_prof = 0;          // tree_prof: diagnostic phase stamps
   uint32_t tree_l = 2048;          // tree_l: k_tree_l (tables in LDS) when the largest document fits: its tile (2048 or 1024; 0 = k_tree)
   uint32_t gdir = 32;              // gdir: MiB of global rank directory a giant document may use
@@ -4546,6 +4546,116 @@ void *scratch(cw_ctx *c, const char *name, size_t bytes) {
 template <typename T>
 T *scratch_t(cw_ctx *c, const char *name, size_t count) {
   return reinterpret_cast<T *>(scratch(c, name, count * sizeof(T)));
+}
+
+// A host array in the scratch buffer `name`: *dst = the device copy (nothing is
+// copied when bytes == 0).  Pageable host memory: blocking copies
+// (hipMemcpyAsync from/to pageable memory is not reliably ordered by a later
+// stream synchronize), so the stream is idle here (the caller's one wait).
+template <typename T>
+int upload(cw_ctx *c, const char *name, const T *src, size_t bytes, const T **dst) {
+  void *p = scratch(c, name, bytes);
+  if (!p) return fail(c, "out of device memory (%s, %zu bytes)", name, bytes);
+  if (bytes) HIPCHK(c, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
+  *dst = static_cast<const T *>(p);
+  return 0;
+}
+
+// The small readback: `bytes` (<= PIN_SMALL_BYTES) of device memory copied to
+// c->pin_small on the stream, then the wait for the stream (NO_WAIT: left to the
+// caller, who enqueues another copy first).  The words, or nullptr after fail().
+constexpr size_t PIN_SMALL_BYTES = 64;
+constexpr bool NO_WAIT = false;
+const uint32_t *read_small(cw_ctx *c, const void *dev, size_t bytes, bool wait = true) {
+  if (bytes > PIN_SMALL_BYTES) return fail(c, "read_small: %zu bytes", bytes), nullptr;
+  if ((!c->pin_small &&
+       hipHostMalloc((void **)&c->pin_small, PIN_SMALL_BYTES, hipHostMallocDefault) != hipSuccess) ||
+      hipMemcpyAsync(c->pin_small, dev, bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      (wait && hipStreamSynchronize(c->stream) != hipSuccess))
+    return fail(c, "small readback: %s", hipGetErrorString(hipGetLastError())), nullptr;
+  return c->pin_small;
+}
+
+// The host-memory form of a list call: the caller's cw_list_result staged in
+// scratch buffers, and copied out afterwards.  Every entry point stages under
+// the same names (hs_*), which holds only while no entry point that stages a
+// result calls another that stages one: cw_weave_lists_k32 calls
+// weave_lists_impl and only the callee stages; cw_merge_lists and cw_weft_lists
+// call weave_lists_device; cw_merge_maps calls weave_maps_impl in device
+// memspace.  Sizes are the superset of what the callers need (max(N, 1) nodes,
+// D + 1 documents).  The optional outputs are present exactly when the
+// caller's are.
+int stage_list_result(cw_ctx *c, const cw_list_result &res, uint64_t N, uint64_t D,
+                      cw_list_result *dres) {
+  const size_t Ns = std::max<uint64_t>(N, 1);
+  cw_list_result &r = *dres;
+  r = res;
+  r.weave_perm = scratch_t<uint32_t>(c, "hs_perm", Ns);
+  r.visible_bits = res.visible_bits ? scratch_t<uint32_t>(c, "hs_bits", (Ns + 31) / 32) : nullptr;
+  r.visible_count = scratch_t<uint32_t>(c, "hs_vcount", D + 1);
+  r.max_ts = res.max_ts ? scratch_t<uint64_t>(c, "hs_maxts", D + 1) : nullptr;
+  r.status = scratch_t<uint32_t>(c, "hs_status", D + 1);
+  r.yarn_perm = res.yarn_perm ? scratch_t<uint32_t>(c, "hs_yarn", Ns) : nullptr;
+  if (!r.weave_perm || !r.visible_count || !r.status || (res.visible_bits && !r.visible_bits) ||
+      (res.max_ts && !r.max_ts) || (res.yarn_perm && !r.yarn_perm))
+    return fail(c, "out of device memory (host-mode staging)");
+  return 0;
+}
+
+// ... and back: N nodes (nothing per node for an empty batch) and D documents
+// of the staged result to the caller's arrays.  Blocking copies: the stream is
+// idle (the caller's wait).
+int unstage_list_result(cw_ctx *c, const cw_list_result &dres, uint64_t N, uint64_t D,
+                        const cw_list_result &res) {
+  if (N) {
+    HIPCHK(c, hipMemcpy(res.weave_perm, dres.weave_perm, N * 4, hipMemcpyDeviceToHost));
+    if (res.visible_bits)
+      HIPCHK(c, hipMemcpy(res.visible_bits, dres.visible_bits, (N + 31) / 32 * 4, hipMemcpyDeviceToHost));
+    if (res.yarn_perm)
+      HIPCHK(c, hipMemcpy(res.yarn_perm, dres.yarn_perm, N * 4, hipMemcpyDeviceToHost));
+  }
+  HIPCHK(c, hipMemcpy(res.visible_count, dres.visible_count, D * 4, hipMemcpyDeviceToHost));
+  if (res.max_ts) HIPCHK(c, hipMemcpy(res.max_ts, dres.max_ts, D * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.status, dres.status, D * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipDeviceSynchronize());
+  return 0;
+}
+
+// Documents with no nodes have no root: CW_STATUS_ROOT joins their status, in
+// host memory (after the copies out) or on the device (on the stream).
+int root_empty_docs(cw_ctx *c, const uint64_t *off, uint64_t D, uint32_t *status, bool dev) {
+  for (uint64_t d = 0; d < D; d++) {
+    if (off[d + 1] != off[d]) continue;
+    if (!dev)
+      status[d] |= CW_STATUS_ROOT;
+    else
+      HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(status + d), CW_STATUS_ROOT, 1, c->stream));
+  }
+  return 0;
+}
+
+// The doc_offsets of a list call, checked before anything else is read: they
+// start at 0 and do not decrease, the batch has fewer than 2^32 - 1 nodes, a
+// document fewer than `one_limit` in a batch of one and `doc_limit` otherwise
+// (0: no limit of its own).  *largest (optional): the largest document.
+int check_doc_offsets(cw_ctx *c, const uint64_t *off, uint64_t D, uint64_t one_limit,
+                      uint64_t doc_limit, uint64_t *largest = nullptr) {
+  if (!off) return fail(c, "doc_offsets is required (host memory)");
+  if (off[0] != 0) return fail(c, "doc_offsets[0] must be 0");
+  if (off[D] >= 0xFFFFFFFFull)
+    return fail(c, "batch too large: N=%llu (limit 2^32-1)", (unsigned long long)off[D]);
+  const uint64_t limit = D == 1 ? one_limit : doc_limit;
+  uint64_t mx = 0;
+  for (uint64_t d = 0; d < D; d++) {
+    if (off[d + 1] < off[d]) return fail(c, "doc_offsets not monotone");
+    const uint64_t nd = off[d + 1] - off[d];
+    if (limit && nd >= limit)
+      return fail(c, "document %llu too large (limit %llu nodes)", (unsigned long long)d,
+                  (unsigned long long)limit - 1);
+    mx = std::max(mx, nd);
+  }
+  if (largest) *largest = mx;
+  return 0;
 }
 
 hipEvent_t get_event(cw_ctx *c) {
@@ -5196,10 +5306,9 @@ int tail_tree_giant(const Tail &w) {
     }
     if (check_launch(c, "glocal")) return -1;
     // the cross children's count sizes their sort (one readback)
-    if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, mtot, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint32_t M = c->pin_small[0];
+    const uint32_t *pm = read_small(c, mtot, 4);
+    if (!pm) return -1;
+    const uint32_t M = pm[0];
     if (M > N) return fail(c, "cross children %u > %u", M, N);
     if (M) {
       const uint32_t TR = (M + TILE - 1) / TILE;
@@ -5583,7 +5692,6 @@ int front_fused(const ListWeave &w, Front *f) {
   uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
   uint16_t *rank16 = scratch_t<uint16_t>(c, "fr_rank16", N);
   f->kbm = scratch_t<uint32_t>(c, "fr_kbm", (size_t)t.T * KBM_WORDS);
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
   if (!big || !rank16 || !f->kbm) return fail(c, "out of device memory (front)");
   HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
   f->sval = w.svA;
@@ -5665,11 +5773,11 @@ int front_fused(const ListWeave &w, Front *f) {
       fprintf(stderr, "front phases (memtime ticks per doc): dir %.0f rank %.0f write %.0f sval %.0f "
               "svwrite %.0f\n", a[0] / D, a[1] / D, a[2] / D, a[3] / D, a[4] / D);
   }
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pin_small[0] == 0) {
+  const uint32_t *pb = read_small(c, big, 8);
+  if (!pb) return -1;
+  if (pb[0] == 0) {
     f->done = true;
-    c->x_hint = c->pin_small[1] != 0;  // flagged documents, for the exact path
+    c->x_hint = pb[1] != 0;  // flagged documents, for the exact path
     if (f->fused_done && f->yarns_fused) {
       Launch L(c, "yarns", (double)N * (1 + 2 + 2 + 4));
       hipLaunchKernelGGL(k_yarn_doc<1024>, dim3((uint32_t)D), dim3(1024), (size_t)yarn_lds_bytes(t.nmax),
@@ -5749,7 +5857,6 @@ int front_dir3(const ListWeave &w, Front *f) {
   uint64_t *dkmin = scratch_t<uint64_t>(c, "fr_kmin", D);
   uint32_t *dgroups = scratch_t<uint32_t>(c, "fr_groups", D);
   uint32_t *big = scratch_t<uint32_t>(c, "fr_big", 4);
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
   if (!dir || !dkmin || !dgroups || !big) return fail(c, "out of device memory (rank directory)");
   HIPCHK(c, hipMemsetAsync(big, 0, 16, c->stream));
   {
@@ -5762,9 +5869,9 @@ int front_dir3(const ListWeave &w, Front *f) {
                        out->max_ts, w.bt->ts_shift, out->status, big);
   }
   if (check_launch(c, "fdir")) return -1;
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, big, 8, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t nbig = c->pin_small[0], gmax = c->pin_small[1];
+  const uint32_t *pb = read_small(c, big, 8);
+  if (!pb) return -1;
+  const uint32_t nbig = pb[0], gmax = pb[1];
   if (nbig) {
     // some document's ids are too sparse for a slot: general path for the batch
     HIPCHK(c, hipMemsetAsync(out->status, 0, D * 4, c->stream));
@@ -6082,7 +6189,6 @@ int weave_lists_dev_all(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id,
   // documents outside the fast path's domain: the literal fold (exact.hip)
   if (exact_fixup(c, bt, id, cause, kind, &dres, x_hint)) return -1;
   return 0;
-
 }
 
 // dev_inputs: id_key / cause_key / kind are device arrays even when the results
@@ -6090,89 +6196,41 @@ int weave_lists_dev_all(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id,
 int weave_lists_impl(cw_ctx *c, const cw_list_batch *bt, cw_list_result *res, int memspace,
                      bool dev_inputs = false) {
   if (!bt || !res) return fail(c, "null batch/result");
-  const uint64_t D = bt->n_docs;
-  if (!bt->doc_offsets) return fail(c, "doc_offsets is required (host memory)");
-  const uint64_t N64 = bt->doc_offsets[D];
-  if (bt->doc_offsets[0] != 0) return fail(c, "doc_offsets[0] must be 0");
-  if (N64 >= 0xFFFFFFFFull) return fail(c, "batch too large: N=%llu (limit 2^32-1)",
-                                        (unsigned long long)N64);
+  const uint64_t D = bt->n_docs, *off = bt->doc_offsets;
   // a one-document batch takes the giant path (wide links) up to 2^31 - 2
   // nodes; in a batch of several documents each stays below 2^29 - 1
-  for (uint64_t d = 0; d < D; d++) {
-    if (bt->doc_offsets[d + 1] < bt->doc_offsets[d]) return fail(c, "doc_offsets not monotone");
-    const uint64_t nd = bt->doc_offsets[d + 1] - bt->doc_offsets[d];
-    if (D == 1 ? nd >= SUCCW_END : nd >= LINK_IDX)
-      return fail(c, "document %llu too large (limit %s nodes)", (unsigned long long)d,
-                  D == 1 ? "2^31-2" : "2^29-2 in a batch of several documents");
-  }
+  if (check_doc_offsets(c, off, D, SUCCW_END, LINK_IDX)) return -1;
   if (!res->weave_perm || !res->visible_count || !res->status)
     return fail(c, "weave_perm, visible_count and status are required");
-  const uint32_t N = (uint32_t)N64;
+  const uint32_t N = (uint32_t)off[D];
+  const bool host = memspace == CW_MEM_HOST;
   HIPCHK(c, hipSetDevice(c->device));
 
   // host tables (cached while the document layout repeats)
-  if (ensure_tables(c, D, bt->doc_offsets)) return -1;
+  if (ensure_tables(c, D, off)) return -1;
 
   const uint64_t *id = bt->id_key, *cause = bt->cause_key;
   const uint8_t *kind = bt->kind;
   cw_list_result dres = *res;
-  if (memspace == CW_MEM_HOST) {
+  if (host) {
     if (N && (!id || !cause || !kind)) return fail(c, "null input arrays");
-    uint64_t *did = dev_inputs ? nullptr : scratch_t<uint64_t>(c, "h_id", N);
-    uint64_t *dca = dev_inputs ? nullptr : scratch_t<uint64_t>(c, "h_cause", N);
-    uint8_t *dk = dev_inputs ? nullptr : scratch_t<uint8_t>(c, "h_kind", N);
-    dres.weave_perm = scratch_t<uint32_t>(c, "h_perm", N);
-    dres.visible_bits = res->visible_bits ? scratch_t<uint32_t>(c, "h_bits", ((size_t)N + 31) / 32) : nullptr;
-    dres.visible_count = scratch_t<uint32_t>(c, "h_vcount", D);
-    dres.max_ts = res->max_ts ? scratch_t<uint64_t>(c, "h_maxts", D) : nullptr;
-    dres.status = scratch_t<uint32_t>(c, "h_status", D);
-    dres.yarn_perm = res->yarn_perm ? scratch_t<uint32_t>(c, "h_yarn", N) : nullptr;
-    if ((!dev_inputs && (!did || !dca || !dk)) || !dres.weave_perm || !dres.visible_count ||
-        !dres.status || (res->visible_bits && !dres.visible_bits) || (res->max_ts && !dres.max_ts) ||
-        (res->yarn_perm && !dres.yarn_perm))
-      return fail(c, "out of device memory (host-mode staging)");
+    if (stage_list_result(c, *res, N, D, &dres)) return -1;
     if (!dev_inputs) {
-      // Pageable host memory: blocking copies (hipMemcpyAsync from/to pageable
-      // memory is not reliably ordered by a later stream synchronize).
       HIPCHK(c, hipStreamSynchronize(c->stream));
-      if (N) {
-        HIPCHK(c, hipMemcpy(did, id, (size_t)N * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(dca, cause, (size_t)N * 8, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(dk, kind, N, hipMemcpyHostToDevice));
-      }
-      id = did;
-      cause = dca;
-      kind = dk;
+      if (upload(c, "h_id", id, (size_t)N * 8, &id) || upload(c, "h_cause", cause, (size_t)N * 8, &cause) ||
+          upload(c, "h_kind", kind, N, &kind))
+        return -1;
     }
   }
   if (weave_lists_dev_all(c, bt, id, cause, kind, &dres)) return -1;
 
-  if (memspace == CW_MEM_HOST) {
+  if (host) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(res->weave_perm, dres.weave_perm, (size_t)N * 4, hipMemcpyDeviceToHost));
-    if (res->visible_bits)
-      HIPCHK(c, hipMemcpy(res->visible_bits, dres.visible_bits, ((size_t)N + 31) / 32 * 4,
-                          hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->visible_count, dres.visible_count, D * 4, hipMemcpyDeviceToHost));
-    if (res->max_ts)
-      HIPCHK(c, hipMemcpy(res->max_ts, dres.max_ts, D * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->status, dres.status, D * 4, hipMemcpyDeviceToHost));
-    if (res->yarn_perm)
-      HIPCHK(c, hipMemcpy(res->yarn_perm, dres.yarn_perm, (size_t)N * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipDeviceSynchronize());
-    // documents with no nodes have no root
-    for (uint64_t d = 0; d < D; d++)
-      if (bt->doc_offsets[d + 1] == bt->doc_offsets[d]) res->status[d] |= CW_STATUS_ROOT;
-  } else {
-    // empty documents: set the ROOT bit on the device
-    for (uint64_t d = 0; d < D; d++)
-      if (bt->doc_offsets[d + 1] == bt->doc_offsets[d])
-        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(res->status + d), CW_STATUS_ROOT, 1,
-                                    c->stream));
-    if (!c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (unstage_list_result(c, dres, N, D, *res)) return -1;
   }
-  if (c->prof) return collect_prof(c);
-  return 0;
+  if (root_empty_docs(c, off, D, res->status, !host)) return -1;
+  if (!host && !c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return c->prof ? collect_prof(c) : 0;
 }
 
 // --- K32: narrow keys (cw_weave_lists_k32) ---------------------------------------
@@ -6200,12 +6258,10 @@ __global__ __launch_bounds__(256) void k_narrow16(const uint32_t *__restrict__ s
 
 int weave_lists_k32_impl(cw_ctx *c, const cw_list_batch_k32 *b, cw_list_result *res, int memspace) {
   if (!b || !res) return fail(c, "null batch/result");
-  if (!b->doc_offsets) return fail(c, "doc_offsets is required (host memory)");
   if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
-  const uint64_t D = b->n_docs, N64 = b->doc_offsets[D];
-  if (N64 >= 0xFFFFFFFFull) return fail(c, "batch too large: N=%llu (limit 2^32-1)",
-                                        (unsigned long long)N64);
-  const uint32_t N = (uint32_t)N64;
+  const uint64_t D = b->n_docs;
+  if (check_doc_offsets(c, b->doc_offsets, D, SUCCW_END, LINK_IDX)) return -1;
+  const uint32_t N = (uint32_t)b->doc_offsets[D];
   const size_t Ns = std::max<uint32_t>(N, 1);
   const uint32_t *id32 = b->id_key, *ca32 = b->cause_key;
   const uint8_t *kind = b->kind;
@@ -6214,16 +6270,10 @@ int weave_lists_k32_impl(cw_ctx *c, const cw_list_batch_k32 *b, cw_list_result *
   uint64_t *wid = scratch_t<uint64_t>(c, "k32_id", Ns), *wca = scratch_t<uint64_t>(c, "k32_cause", Ns);
   if (!wid || !wca) return fail(c, "out of device memory (k32)");
   if (memspace == CW_MEM_HOST && N) {
-    uint32_t *d32 = scratch_t<uint32_t>(c, "k32_h", 2 * Ns);
-    uint8_t *dk = scratch_t<uint8_t>(c, "h_kind", Ns);
-    if (!d32 || !dk) return fail(c, "out of device memory (k32 staging)");
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(d32, id32, (size_t)N * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d32 + Ns, ca32, (size_t)N * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(dk, kind, N, hipMemcpyHostToDevice));
-    id32 = d32;
-    ca32 = d32 + Ns;
-    kind = dk;
+    if (upload(c, "k32_hid", id32, (size_t)N * 4, &id32) || upload(c, "k32_hca", ca32, (size_t)N * 4, &ca32) ||
+        upload(c, "h_kind", kind, N, &kind))
+      return -1;
   }
   if (N) {
     Launch L(c, "widen32", (double)N * (4 + 4 + 8 + 8));
@@ -6640,22 +6690,59 @@ int weave_ranked_impl(cw_ctx *c, const cw_ranked_list *in, cw_list_result *out) 
   if (check_launch(c, "ranked_check")) return -1;
   if (weave_tail(c, 1, n, true, in->par, in->kind, in->val, nullptr, nullptr, 0, out)) return -1;
   {  // flagged (orphan / non-Lamport / root): the literal fold (exact.hip)
-    if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, out->status, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if ((c->pin_small[0] & X_MASK) && !(c->pin_small[0] & CW_STATUS_DUP) && exact_ranked(c, in, out))
-      return -1;
+    const uint32_t *st = read_small(c, out->status, 4);
+    if (!st) return -1;
+    if ((st[0] & X_MASK) && !(st[0] & CW_STATUS_DUP) && exact_ranked(c, in, out)) return -1;
   }
   if (!c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->prof) return collect_prof(c);
-  return 0;
+  return c->prof ? collect_prof(c) : 0;
 }
 
 // Key weaves of at most this many documents / nodes go through one list call
 // (keeps every launch grid of the list pipeline inside the dispatch limits).
 constexpr uint64_t MAP_CHUNK_DOCS = 1ull << 20, MAP_CHUNK_NODES = 1ull << 30;
 
-int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int memspace) {
+// What the stages of one cw_weave_maps call share (maps_*, in call order).
+struct MapWeave {
+  cw_ctx *c;
+  const cw_map_batch *bt;
+  cw_map_result *res;
+  bool dev;                        // inputs and results are device memory
+  uint64_t D, S;                   // collections; key weaves
+  uint32_t N;                      // nodes
+  size_t NL;                       // nodes of the key weaves as lists: N + one root each
+  const uint64_t *id, *cause;      // the inputs in device memory
+  const uint8_t *cis, *kind;
+  uint32_t key_bits, W;            // bits of the ids; of the widest of tokens, ids and causes
+  uint64_t *skey, *segk, *ks;      // sorted ids (1), the key per sorted node (2), keys grouped (3)
+  uint32_t *sval, *mpar, *rank_s;  // ... input index, parent in the key weave, place in key order
+  uint8_t *mkind;
+  uint32_t *status, *tsb, *small;  // per collection; key weaves before each tile; [S, max_len]
+  uint32_t *seg_of, *seg_start, *seg_coll, *lmap, *lperm, *lvc, *lst;
+  uint64_t *seg_key, *seg_off, *lid, *lcause;  // (l*: the key weaves as list documents)
+  uint8_t *lkind;
+  bool tiny;                       // every key weave fits one wave (k_small_weave)
+};
+
+// The collection layout: monotone, every collection below the list limit.
+int maps_check_layout(cw_ctx *c, const cw_map_batch *bt) {
+  const uint64_t *o = bt->coll_offsets, D = bt->n_colls;
+  uint64_t back = 0, big = 0, mx = 0;
+  for (uint64_t d = 0; d < D; d++) {  // branch-free: vectorizes
+    back |= (uint64_t)(o[d + 1] < o[d]);
+    big |= (uint64_t)(o[d + 1] - o[d] >= LINK_IDX - 1);
+    mx = std::max<uint64_t>(mx, o[d + 1] - o[d]);
+  }
+  c->mpack.maxcoll = mx;
+  if (back) return fail(c, "coll_offsets not monotone");
+  if (big)
+    for (uint64_t d = 0; d < D; d++)
+      if (o[d + 1] - o[d] >= LINK_IDX - 1) return fail(c, "collection %llu too large", (unsigned long long)d);
+  return 0;
+}
+
+// The arguments, and whether the layout is the previous call's.
+int maps_check(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int memspace) {
   if (!bt || !res) return fail(c, "null batch/result");
   if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
   const bool dev = memspace == CW_MEM_DEVICE;
@@ -6682,228 +6769,190 @@ int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int m
     c->mpack.same = c->mpack.off.size() == D + 1 &&
                     memcmp(c->mpack.off.data(), bt->coll_offsets, (D + 1) * 8) == 0;
   }
-  auto check_layout = [&]() -> int {
-    const uint64_t *o = bt->coll_offsets;
-    uint64_t back = 0, big = 0, mx = 0;
-    for (uint64_t d = 0; d < D; d++) {  // branch-free: vectorizes
-      back |= (uint64_t)(o[d + 1] < o[d]);
-      big |= (uint64_t)(o[d + 1] - o[d] >= LINK_IDX - 1);
-      mx = std::max<uint64_t>(mx, o[d + 1] - o[d]);
-    }
-    c->mpack.maxcoll = mx;
-    if (back) return fail(c, "coll_offsets not monotone");
-    if (big)
-      for (uint64_t d = 0; d < D; d++)
-        if (o[d + 1] - o[d] >= LINK_IDX - 1) return fail(c, "collection %llu too large", (unsigned long long)d);
-    return 0;
-  };
-  if (!c->mpack.same && check_layout()) return -1;
+  if (!c->mpack.same && maps_check_layout(c, bt)) return -1;
   if (!res->seg_offsets || !res->seg_coll || !res->seg_key || !res->seg_active ||
       !res->seg_perm || !res->status)
     return fail(c, "every cw_map_result array is required");
   if (bt->token_bits == 0 || bt->token_bits > 62) return fail(c, "token_bits must be 1..62");
-  const uint32_t N = (uint32_t)N64;
-  HIPCHK(c, hipSetDevice(c->device));
-  res->n_segs = 0;
-  if (N == 0) {
-    if (dev) {
-      HIPCHK(c, hipMemsetAsync(res->status, 0, D * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(res->seg_offsets, 0, 8, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-    } else {
-      memset(res->status, 0, D * 4);
-      res->seg_offsets[0] = 0;
-    }
-    return 0;
-  }
-  if (!bt->id_key || !bt->cause || !bt->cause_is_id || !bt->kind)
+  if (N64 && (!bt->id_key || !bt->cause || !bt->cause_is_id || !bt->kind))
     return fail(c, "null input arrays");
+  return 0;
+}
 
-  const uint64_t *id = dev ? bt->id_key : scratch_t<uint64_t>(c, "m_id", N);
-  const uint64_t *cause = dev ? bt->cause : scratch_t<uint64_t>(c, "m_cause", N);
-  const uint8_t *cis = dev ? bt->cause_is_id : scratch_t<uint8_t>(c, "m_cis", N);
-  const uint8_t *kind = dev ? bt->kind : scratch_t<uint8_t>(c, "m_kind", N);
-  if (!id || !cause || !cis || !kind) return fail(c, "out of device memory (maps, N=%u)", N);
-  if (!dev) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy((void *)id, bt->id_key, (size_t)N * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy((void *)cause, bt->cause, (size_t)N * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy((void *)cis, bt->cause_is_id, N, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy((void *)kind, bt->kind, N, hipMemcpyHostToDevice));
-  }
-  if (c->map_fused) {  // small collections: one kernel (mappack.hip)
-    int rc = weave_maps_packed(c, bt, res, dev, id, cause, cis, kind);
-    if (rc == 2) {  // the speculated layout was not the cached one: check it, weave again
-      c->mpack.same = false;
-      c->mpack.verify = false;
-      if (check_layout()) return -1;
-      rc = weave_maps_packed(c, bt, res, dev, id, cause, cis, kind);
-    }
-    if (rc <= 0) return rc;
-  }
-  // significant bits of the ids and of the causes (id keys, SURVEY F8c, are
-  // cause ids, which may lie outside the collection): one reduction, one readback
-  uint32_t key_bits = bt->key_bits, cause_bits = 0;
-  {
-    unsigned long long *red = scratch_t<unsigned long long>(c, "red2", 2);
-    if (!red) return fail(c, "out of device memory (red)");
-    HIPCHK(c, hipMemsetAsync(red, 0, 16, c->stream));
-    hipLaunchKernelGGL(k_or_reduce2, dim3(1024), dim3(256), 0, c->stream, id, cause, N, red);
-    if (check_launch(c, "or_reduce2")) return -1;
-    if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, red, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const uint64_t *v = reinterpret_cast<const uint64_t *>(c->pin_small);
-    const uint32_t ib = v[0] ? 64 - __builtin_clzll(v[0]) : 1, cb = v[1] ? 64 - __builtin_clzll(v[1]) : 1;
-    if (key_bits == 0) key_bits = ib;
-    cause_bits = cb;
-  }
-  if (key_bits > 62 || cause_bits > 62)
-    return fail(c, "map ids need %u bits (limit 62)", std::max(key_bits, cause_bits));
+// Significant bits of the ids and of the causes (id keys, SURVEY F8c, are
+// cause ids, which may lie outside the collection): one reduction, one readback.
+int maps_key_bits(MapWeave &m) {
+  cw_ctx *c = m.c;
+  unsigned long long *red = scratch_t<unsigned long long>(c, "red2", 2);
+  if (!red) return fail(c, "out of device memory (red)");
+  HIPCHK(c, hipMemsetAsync(red, 0, 16, c->stream));
+  hipLaunchKernelGGL(k_or_reduce2, dim3(1024), dim3(256), 0, c->stream, m.id, m.cause, m.N, red);
+  if (check_launch(c, "or_reduce2")) return -1;
+  const uint64_t *v = reinterpret_cast<const uint64_t *>(read_small(c, red, 16));
+  if (!v) return -1;
+  const uint32_t ib = v[0] ? 64 - __builtin_clzll(v[0]) : 1, cb = v[1] ? 64 - __builtin_clzll(v[1]) : 1;
+  m.key_bits = m.bt->key_bits ? m.bt->key_bits : ib;
+  if (m.key_bits > 62 || cb > 62)
+    return fail(c, "map ids need %u bits (limit 62)", std::max(m.key_bits, cb));
+  m.W = std::max(std::max(m.bt->token_bits, m.key_bits), cb);
+  return 0;
+}
 
-  // the general path: collection tables (id sort, key resolution and key
-  // grouping run per collection), then every key weave through a list weave
-  if (ensure_tables(c, D, bt->coll_offsets)) return -1;
-  auto &t = c->tab;
-  const uint32_t T = t.T;
-  uint32_t *status = scratch_t<uint32_t>(c, "m_status", D);
+// The general path runs per collection: collection tables, then
+// 1. (sort (::s/nodes ct)) per collection -- map.cljc:28
+// 2. key and cause-in-weave per node -- map.cljc:31-37
+int maps_sort_and_key(MapWeave &m) {
+  cw_ctx *c = m.c;
+  const uint32_t N = m.N;
+  if (ensure_tables(c, m.D, m.bt->coll_offsets)) return -1;
+  const uint32_t T = c->tab.T;
+  m.status = scratch_t<uint32_t>(c, "m_status", m.D);
   uint64_t *skA = scratch_t<uint64_t>(c, "skA", N), *skB = scratch_t<uint64_t>(c, "skB", N);
   uint32_t *svA = scratch_t<uint32_t>(c, "svA", N), *svB = scratch_t<uint32_t>(c, "svB", N);
-  uint64_t *segk = scratch_t<uint64_t>(c, "m_segk", N);
-  uint32_t *mpar = scratch_t<uint32_t>(c, "m_mpar", N);
-  uint8_t *mkind = scratch_t<uint8_t>(c, "m_mkind", N);
-  uint64_t *kA = scratch_t<uint64_t>(c, "m_kA", N), *kB = scratch_t<uint64_t>(c, "m_kB", N);
-  uint32_t *vA = scratch_t<uint32_t>(c, "m_vA", N), *vB = scratch_t<uint32_t>(c, "m_vB", N);
-  uint32_t *tcnt = scratch_t<uint32_t>(c, "m_tcnt", T), *tsb = scratch_t<uint32_t>(c, "m_tsb", T);
-  uint32_t *seg_of = scratch_t<uint32_t>(c, "m_segof", N);
-  if (!status || !skA || !skB || !svA || !svB || !segk ||
-      !mpar || !mkind || !kA || !kB || !vA || !vB || !tcnt || !tsb || !seg_of)
+  m.segk = scratch_t<uint64_t>(c, "m_segk", N);
+  m.mpar = scratch_t<uint32_t>(c, "m_mpar", N);
+  m.mkind = scratch_t<uint8_t>(c, "m_mkind", N);
+  if (!m.status || !skA || !skB || !svA || !svB || !m.segk || !m.mpar || !m.mkind)
     return fail(c, "out of device memory (maps, N=%u)", N);
-  if (!grid_ok(T, SORT_THREADS) || !grid_ok(D, 1024)) return fail(c, "batch too large for one dispatch");
-  HIPCHK(c, hipMemsetAsync(status, 0, D * 4, c->stream));
-  const uint32_t W = std::max(std::max(bt->token_bits, key_bits), cause_bits);
-
-  // 1. (sort (::s/nodes ct)) per collection -- map.cljc:28
-  uint64_t *skey;
-  uint32_t *sval;
-  if (radix_sort<uint64_t>(c, "m_idsort", id, nullptr, skA, svA, skB, svB, key_bits, 0, N, &skey,
-                           &sval))
+  if (!grid_ok(T, SORT_THREADS) || !grid_ok(m.D, 1024)) return fail(c, "batch too large for one dispatch");
+  HIPCHK(c, hipMemsetAsync(m.status, 0, m.D * 4, c->stream));
+  if (radix_sort<uint64_t>(c, "m_idsort", m.id, nullptr, skA, svA, skB, svB, m.key_bits, 0, N, &m.skey,
+                           &m.sval))
     return -1;
-  // 2. key and cause-in-weave per node -- map.cljc:31-37
   {
     Launch L(c, "m_key", (double)N * (8 + 4 + 8 + 1 + 1 + 8 + 4 + 1) + (double)N * 2 * 8);
-    hipLaunchKernelGGL(k_map_key, dim3(T), dim3(256), 0, c->stream, skey, sval, cause, cis, kind,
+    hipLaunchKernelGGL(k_map_key, dim3(T), dim3(256), 0, c->stream, m.skey, m.sval, m.cause, m.cis, m.kind,
                        dev_tab(c, "t_tile_start"), dev_tab(c, "t_tile_doc"),
-                       dev_tab(c, "t_doc_off"), bt->token_bits, W, segk, mpar, mkind, status);
+                       dev_tab(c, "t_doc_off"), m.bt->token_bits, m.W, m.segk, m.mpar, m.mkind, m.status);
   }
-  if (check_launch(c, "m_key")) return -1;
-  // 3. stable grouping by key (id order kept inside a key)
-  uint64_t *ks;
-  uint32_t *rank_s;
-  if (radix_sort<uint64_t>(c, "m_keysort", segk, nullptr, kA, vA, kB, vB, W + 2, 0, N, &ks,
-                           &rank_s))
+  return check_launch(c, "m_key");
+}
+
+// 3. stable grouping by key (id order kept inside a key): the key weaves
+// before each tile (device scan) and their number S (one readback).
+int maps_group(MapWeave &m) {
+  cw_ctx *c = m.c;
+  const uint32_t N = m.N, T = c->tab.T, nb = (T + 1023) / 1024;
+  uint64_t *kA = scratch_t<uint64_t>(c, "m_kA", N), *kB = scratch_t<uint64_t>(c, "m_kB", N);
+  uint32_t *vA = scratch_t<uint32_t>(c, "m_vA", N), *vB = scratch_t<uint32_t>(c, "m_vB", N);
+  uint32_t *tcnt = scratch_t<uint32_t>(c, "m_tcnt", T);
+  uint32_t *chunk = scratch_t<uint32_t>(c, "m_chunk", nb + 1);
+  m.tsb = scratch_t<uint32_t>(c, "m_tsb", T);
+  m.small = scratch_t<uint32_t>(c, "m_small", 4);
+  if (!kA || !kB || !vA || !vB || !tcnt || !chunk || !m.tsb || !m.small)
+    return fail(c, "out of device memory (maps, N=%u)", N);
+  if (radix_sort<uint64_t>(c, "m_keysort", m.segk, nullptr, kA, vA, kB, vB, m.W + 2, 0, N, &m.ks,
+                           &m.rank_s))
     return -1;
   {
     Launch L(c, "m_segcount", (double)N * 8);
-    hipLaunchKernelGGL(k_seg_count, dim3(T), dim3(256), 0, c->stream, ks,
+    hipLaunchKernelGGL(k_seg_count, dim3(T), dim3(256), 0, c->stream, m.ks,
                        dev_tab(c, "t_tile_start"), dev_tab(c, "t_tile_doc"),
                        dev_tab(c, "t_doc_off"), tcnt);
   }
   if (check_launch(c, "m_segcount")) return -1;
-  // key weaves before each tile (device scan) and their number S (one readback)
-  uint32_t *chunk = scratch_t<uint32_t>(c, "m_chunk", (T + 1023) / 1024 + 1);
-  uint32_t *small = scratch_t<uint32_t>(c, "m_small", 4);
-  if (!chunk || !small) return fail(c, "out of device memory (maps scan)");
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-  HIPCHK(c, hipMemsetAsync(small, 0, 16, c->stream));
-  {
-    const uint32_t nb = (T + 1023) / 1024;
-    hipLaunchKernelGGL(k_scan_chunks, dim3(nb), dim3(1024), 0, c->stream, tcnt, T, tsb, chunk);
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, c->stream, chunk, nb, small);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, c->stream, tsb, T, chunk);
-  }
+  HIPCHK(c, hipMemsetAsync(m.small, 0, 16, c->stream));
+  hipLaunchKernelGGL(k_scan_chunks, dim3(nb), dim3(1024), 0, c->stream, tcnt, T, m.tsb, chunk);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, c->stream, chunk, nb, m.small);
+  hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(1024), 0, c->stream, m.tsb, T, chunk);
   if (check_launch(c, "m_scan")) return -1;
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, small, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t S = c->pin_small[0];
-  if (S > res->cap_segs)
-    return fail(c, "cap_segs too small: %llu key weaves", (unsigned long long)S);
-  uint32_t *seg_start = scratch_t<uint32_t>(c, "m_segstart", S + 1);
-  uint32_t *seg_coll = scratch_t<uint32_t>(c, "m_segcoll", S);
-  uint64_t *seg_key = scratch_t<uint64_t>(c, "m_segkey", S);
-  const size_t NL = (size_t)N + S;
-  uint64_t *lid = scratch_t<uint64_t>(c, "m_lid", NL), *lcause = scratch_t<uint64_t>(c, "m_lcause", NL);
-  uint8_t *lkind = scratch_t<uint8_t>(c, "m_lkind", NL);
-  uint32_t *lmap = scratch_t<uint32_t>(c, "m_lmap", NL), *lperm = scratch_t<uint32_t>(c, "m_lperm", NL);
-  uint32_t *lvc = scratch_t<uint32_t>(c, "m_lvc", S), *lst = scratch_t<uint32_t>(c, "m_lst", S);
-  uint64_t *seg_off = scratch_t<uint64_t>(c, "m_segoff", S + 1);
-  uint32_t *seg_perm = scratch_t<uint32_t>(c, "m_segperm", NL);
-  int64_t *seg_act = scratch_t<int64_t>(c, "m_segact", S);
-  if (!seg_start || !seg_coll || !seg_key || !lid || !lcause || !lkind || !lmap || !lperm || !lvc ||
-      !lst || !seg_off || !seg_perm || !seg_act)
+  const uint32_t *p = read_small(c, m.small, 4);
+  if (!p) return -1;
+  m.S = p[0];
+  m.NL = (size_t)N + m.S;
+  if (m.S > m.res->cap_segs) return fail(c, "cap_segs too small: %llu key weaves", (unsigned long long)m.S);
+  return 0;
+}
+
+// The key weaves as list documents: key weave s = list document
+// [seg_start[s] + s, seg_start[s+1] + s + 1), a root in front of its nodes.
+int maps_build_lists(MapWeave &m) {
+  cw_ctx *c = m.c;
+  const uint32_t N = m.N, T = c->tab.T;
+  const uint64_t S = m.S;
+  const size_t NL = m.NL;
+  m.seg_of = scratch_t<uint32_t>(c, "m_segof", N);
+  m.seg_start = scratch_t<uint32_t>(c, "m_segstart", S + 1);
+  m.seg_coll = scratch_t<uint32_t>(c, "m_segcoll", S);
+  m.seg_key = scratch_t<uint64_t>(c, "m_segkey", S);
+  m.seg_off = scratch_t<uint64_t>(c, "m_segoff", S + 1);
+  m.lid = scratch_t<uint64_t>(c, "m_lid", NL), m.lcause = scratch_t<uint64_t>(c, "m_lcause", NL);
+  m.lkind = scratch_t<uint8_t>(c, "m_lkind", NL);
+  m.lmap = scratch_t<uint32_t>(c, "m_lmap", NL), m.lperm = scratch_t<uint32_t>(c, "m_lperm", NL);
+  m.lvc = scratch_t<uint32_t>(c, "m_lvc", S), m.lst = scratch_t<uint32_t>(c, "m_lst", S);
+  if (!m.seg_of || !m.seg_start || !m.seg_coll || !m.seg_key || !m.seg_off || !m.lid || !m.lcause ||
+      !m.lkind || !m.lmap || !m.lperm || !m.lvc || !m.lst)
     return fail(c, "out of device memory (maps, S=%llu)", (unsigned long long)S);
   {
     Launch L(c, "m_segmark", (double)N * (8 + 4) + (double)S * (4 + 4 + 8));
-    hipLaunchKernelGGL(k_seg_mark, dim3(T), dim3(256), 0, c->stream, ks,
+    hipLaunchKernelGGL(k_seg_mark, dim3(T), dim3(256), 0, c->stream, m.ks,
                        dev_tab(c, "t_tile_start"), dev_tab(c, "t_tile_doc"),
-                       dev_tab(c, "t_doc_off"), tsb, W, seg_of, seg_start, seg_coll, seg_key);
+                       dev_tab(c, "t_doc_off"), m.tsb, m.W, m.seg_of, m.seg_start, m.seg_coll, m.seg_key);
   }
   if (check_launch(c, "m_segmark")) return -1;
   {
     Launch L(c, "m_segbuild", (double)N * (4 + 4 + 4 + 8 + 4 + 8 + 1 + 8 + 8 + 1 + 4));
-    hipLaunchKernelGGL(k_seg_build, dim3((N + 255) / 256), dim3(256), 0, c->stream, skey, sval,
-                       cause, mpar, mkind, rank_s, seg_of, seg_coll, dev_tab(c, "t_doc_off"), N, lid,
-                       lcause, lkind, lmap);
+    hipLaunchKernelGGL(k_seg_build, dim3((N + 255) / 256), dim3(256), 0, c->stream, m.skey, m.sval,
+                       m.cause, m.mpar, m.mkind, m.rank_s, m.seg_of, m.seg_coll, dev_tab(c, "t_doc_off"), N,
+                       m.lid, m.lcause, m.lkind, m.lmap);
   }
   if (check_launch(c, "m_segbuild")) return -1;
   {
     Launch L(c, "m_segroots", (double)S * 25);
     hipLaunchKernelGGL(k_seg_roots, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, c->stream,
-                       seg_start, (uint32_t)S, lid, lcause, lkind, lmap);
+                       m.seg_start, (uint32_t)S, m.lid, m.lcause, m.lkind, m.lmap);
   }
   if (check_launch(c, "m_segroots")) return -1;
-
-  // key weave s = list document [seg_start[s] + s, seg_start[s+1] + s + 1)
   {
     Launch L(c, "m_segoff", (double)S * 12);
     hipLaunchKernelGGL(k_seg_off, dim3((uint32_t)std::min<uint64_t>((S + 256) / 256, 2048)), dim3(256),
-                       0, c->stream, seg_start, (uint32_t)S, N, seg_off, small + 1);
+                       0, c->stream, m.seg_start, (uint32_t)S, N, m.seg_off, m.small + 1);
   }
   if (check_launch(c, "m_segoff")) return -1;
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, small + 1, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint64_t max_len = c->pin_small[0];
-  std::vector<uint64_t> loff;  // host copy, only for the list pipeline's chunks
-  if (!(c->map_small && max_len <= SMALL_MAX)) {
-    loff.resize(S + 1);
-    HIPCHK(c, hipMemcpy(loff.data(), seg_off, (S + 1) * 8, hipMemcpyDeviceToHost));
-  }
+  const uint32_t *max_len = read_small(c, m.small + 1, 4);
+  if (!max_len) return -1;
+  m.tiny = c->map_small && max_len[0] <= SMALL_MAX;
+  return 0;
+}
 
-  // 4. every key weave is a list weave -- (s/weave-node key-weave ...), map.cljc:40-41
-  if (c->map_small && max_len <= SMALL_MAX) {
+// 4. every key weave is a list weave -- (s/weave-node key-weave ...), map.cljc:40-41
+int maps_weave_keys(MapWeave &m) {
+  cw_ctx *c = m.c;
+  const uint64_t S = m.S;
+  std::vector<uint64_t> loff;  // seg_off in host memory: once, only when the list pipeline runs
+  auto host_offsets = [&]() -> int {
+    if (!loff.empty()) return 0;
+    loff.resize(S + 1);
+    HIPCHK(c, hipMemcpy(loff.data(), m.seg_off, (S + 1) * 8, hipMemcpyDeviceToHost));
+    return 0;
+  };
+  // key weaves [s0, s0 + n) as a list batch of the offsets `off`, relative to loff[s0]
+  cw_list_batch lb{};
+  cw_list_result lr{};
+  lb.key_bits = m.key_bits;
+  auto key_lists = [&](uint64_t s0, uint64_t n, const uint64_t *off) {
+    lb.n_docs = n, lb.doc_offsets = off;
+    lr.weave_perm = m.lperm + loff[s0], lr.visible_count = m.lvc + s0, lr.status = m.lst + s0;
+  };
+  if (m.tiny) {
     // key weaves are tiny (config 4: a few nodes per key): one wave each
-    Launch L(c, "m_small", (double)NL * (8 + 8 + 1 + 4) + (double)S * 12);
-    hipLaunchKernelGGL(k_small_weave, dim3((uint32_t)((NL + SMALL_CHUNK - 1) / SMALL_CHUNK)),
-                       dim3(SMALL_SLOTS), 0, c->stream, seg_off, (uint32_t)S, lid, lcause, lkind,
-                       lperm, lst);
+    Launch L(c, "m_small", (double)m.NL * (8 + 8 + 1 + 4) + (double)S * 12);
+    hipLaunchKernelGGL(k_small_weave, dim3((uint32_t)((m.NL + SMALL_CHUNK - 1) / SMALL_CHUNK)),
+                       dim3(SMALL_SLOTS), 0, c->stream, m.seg_off, (uint32_t)S, m.lid, m.lcause, m.lkind,
+                       m.lperm, m.lst);
+  } else if (host_offsets()) {
+    return -1;
   }
   if (check_launch(c, "m_small")) return -1;
   std::vector<uint64_t> rel;
-  for (uint64_t s0 = (c->map_small && max_len <= SMALL_MAX) ? S : 0; s0 < S;) {
+  for (uint64_t s0 = m.tiny ? S : 0; s0 < S;) {
     uint64_t s1 = s0 + 1;
     while (s1 < S && s1 - s0 < MAP_CHUNK_DOCS && loff[s1 + 1] - loff[s0] <= MAP_CHUNK_NODES) s1++;
     rel.resize(s1 - s0 + 1);
     for (uint64_t sg = s0; sg <= s1; sg++) rel[sg - s0] = loff[sg] - loff[s0];
     if (ensure_tables(c, s1 - s0, rel.data())) return -1;
-    cw_list_batch lb{};
-    lb.n_docs = s1 - s0;
-    lb.doc_offsets = rel.data();
-    lb.key_bits = key_bits;
-    cw_list_result lr{};
-    lr.weave_perm = lperm + loff[s0];
-    lr.visible_count = lvc + s0;
-    lr.status = lst + s0;
-    if (weave_lists_device(c, &lb, lid + loff[s0], lcause + loff[s0], lkind + loff[s0], &lr))
+    key_lists(s0, s1 - s0, rel.data());
+    if (weave_lists_device(c, &lb, m.lid + loff[s0], m.lcause + loff[s0], m.lkind + loff[s0], &lr))
       return -1;
     s0 = s1;
   }
@@ -6911,57 +6960,100 @@ int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int m
   // appended orphans next to children of the root, a cause with a larger id
   // than its node (map.cljc:40-41 folds them whatever their causes) -- by the
   // literal fold (exact.hip), as the fused path's literal key weaves
-  {
-    HIPCHK(c, hipMemsetAsync(small, 0, 4, c->stream));
-    hipLaunchKernelGGL(k_xcount_nonempty, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, c->stream,
-                       lst, (uint32_t)S, small);
-    if (check_launch(c, "m_xcount")) return -1;
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, small, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->pin_small[0]) {
-      if (loff.empty()) {
-        loff.resize(S + 1);
-        HIPCHK(c, hipMemcpy(loff.data(), seg_off, (S + 1) * 8, hipMemcpyDeviceToHost));
-      }
-      cw_list_batch lb{};
-      lb.n_docs = S;
-      lb.doc_offsets = loff.data();
-      lb.key_bits = key_bits;
-      cw_list_result lr{};
-      lr.weave_perm = lperm;
-      lr.visible_count = lvc;
-      lr.status = lst;
-      c->x_pending = false;  // (a chunk's giant key weave left its own status there)
-      if (exact_fixup(c, &lb, lid, lcause, lkind, &lr, true)) return -1;
-    }
+  HIPCHK(c, hipMemsetAsync(m.small, 0, 4, c->stream));
+  hipLaunchKernelGGL(k_xcount_nonempty, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, c->stream,
+                     m.lst, (uint32_t)S, m.small);
+  if (check_launch(c, "m_xcount")) return -1;
+  const uint32_t *flagged = read_small(c, m.small, 4);
+  if (!flagged) return -1;
+  if (flagged[0]) {
+    if (host_offsets()) return -1;
+    key_lists(0, S, loff.data());
+    c->x_pending = false;  // (a chunk's giant key weave left its own status there)
+    if (exact_fixup(c, &lb, m.lid, m.lcause, m.lkind, &lr, true)) return -1;
   }
+  return 0;
+}
 
-  // 5. key weaves in collection-local input indices, active-node per key
+// 5. key weaves in collection-local input indices, active-node per key; the
+// results to the caller.
+int maps_finish(MapWeave &m) {
+  cw_ctx *c = m.c;
+  cw_map_result *res = m.res;
+  const uint64_t S = m.S;
+  const size_t NL = m.NL;
+  uint32_t *seg_perm = scratch_t<uint32_t>(c, "m_segperm", NL);
+  int64_t *seg_act = scratch_t<int64_t>(c, "m_segact", S);
+  if (!seg_perm || !seg_act) return fail(c, "out of device memory (maps, S=%llu)", (unsigned long long)S);
   {
-    Launch L(c, "m_segperm", (double)N * (4 + 4 + 8 + 4 + 4) + (double)S * 4);
+    Launch L(c, "m_segperm", (double)m.N * (4 + 4 + 8 + 4 + 4) + (double)S * 4);
     hipLaunchKernelGGL(k_seg_perm, dim3((uint32_t)((NL + 255) / 256)), dim3(256), 0, c->stream,
-                       lperm, lmap, seg_off, seg_of, seg_start, N, (uint32_t)S, seg_perm);
+                       m.lperm, m.lmap, m.seg_off, m.seg_of, m.seg_start, m.N, (uint32_t)S, seg_perm);
   }
   if (check_launch(c, "m_segperm")) return -1;
   {
     Launch L(c, "m_active", (double)S * (16 + 4 + 4 + 8 + 3 * 9));
     hipLaunchKernelGGL(k_seg_active, dim3((uint32_t)((S + 255) / 256)), dim3(256), 0, c->stream,
-                       lperm, lkind, seg_perm, seg_off, seg_coll, lst, (uint32_t)S, seg_act,
-                       status);
+                       m.lperm, m.lkind, seg_perm, m.seg_off, m.seg_coll, m.lst, (uint32_t)S, seg_act,
+                       m.status);
   }
   if (check_launch(c, "m_active")) return -1;
 
-  const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  const hipMemcpyKind out_kind = m.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
   HIPCHK(c, hipMemcpyAsync(res->seg_perm, seg_perm, NL * 4, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_offsets, seg_off, (S + 1) * 8, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_coll, seg_coll, S * 4, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_key, seg_key, S * 8, out_kind, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_offsets, m.seg_off, (S + 1) * 8, out_kind, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_coll, m.seg_coll, S * 4, out_kind, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_key, m.seg_key, S * 8, out_kind, c->stream));
   HIPCHK(c, hipMemcpyAsync(res->seg_active, seg_act, S * 8, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->status, status, D * 4, out_kind, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->status, m.status, m.D * 4, out_kind, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   res->n_segs = S;
-  if (c->prof) return collect_prof(c);
   return 0;
+}
+
+// cw_weave_maps: the one-kernel weave of small collections, else the general
+// path: every key weave through a list weave.
+int weave_maps_impl(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, int memspace) {
+  if (maps_check(c, bt, res, memspace)) return -1;
+  MapWeave m{};
+  m.c = c, m.bt = bt, m.res = res;
+  m.dev = memspace == CW_MEM_DEVICE;
+  m.D = bt->n_colls;
+  m.N = (uint32_t)bt->coll_offsets[m.D];
+  HIPCHK(c, hipSetDevice(c->device));
+  res->n_segs = 0;
+  if (m.N == 0) {  // no key weave
+    if (m.dev) {
+      HIPCHK(c, hipMemsetAsync(res->status, 0, m.D * 4, c->stream));
+      HIPCHK(c, hipMemsetAsync(res->seg_offsets, 0, 8, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else {
+      memset(res->status, 0, m.D * 4);
+      res->seg_offsets[0] = 0;
+    }
+    return 0;
+  }
+  m.id = bt->id_key, m.cause = bt->cause, m.cis = bt->cause_is_id, m.kind = bt->kind;
+  if (!m.dev) {  // the inputs in device memory
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (upload(c, "m_id", m.id, (size_t)m.N * 8, &m.id) ||
+        upload(c, "m_cause", m.cause, (size_t)m.N * 8, &m.cause) ||
+        upload(c, "m_cis", m.cis, m.N, &m.cis) || upload(c, "m_kind", m.kind, m.N, &m.kind))
+      return -1;
+  }
+  if (c->map_fused) {  // small collections: one kernel (mappack.hip)
+    int rc = weave_maps_packed(c, bt, res, m.dev, m.id, m.cause, m.cis, m.kind);
+    if (rc == 2) {  // the speculated layout was not the cached one: check it, weave again
+      c->mpack.same = c->mpack.verify = false;
+      if (maps_check_layout(c, bt)) return -1;
+      rc = weave_maps_packed(c, bt, res, m.dev, m.id, m.cause, m.cis, m.kind);
+    }
+    if (rc <= 0) return rc;  // (1: a collection too large for a pack, the general path)
+  }
+  if (maps_key_bits(m) || maps_sort_and_key(m) || maps_group(m) || maps_build_lists(m) ||
+      maps_weave_keys(m) || maps_finish(m))
+    return -1;
+  return c->prof ? collect_prof(c) : 0;
 }
 
 // The two sides of a merge call, checked before anything is read from the
@@ -6991,17 +7083,6 @@ int check_merge_sides(cw_ctx *c, const B *bt, const void *res, int memspace, con
     if (largest) mx = std::max(mx, n);
   }
   if (largest) *largest = mx;
-  return 0;
-}
-
-// A host array in the scratch buffer `name`: *dst = the device copy (nothing is
-// copied when bytes == 0).  The stream is idle (the caller's wait).
-template <typename T>
-int upload(cw_ctx *c, const char *name, const T *src, size_t bytes, const T **dst) {
-  void *p = scratch(c, name, bytes);
-  if (!p) return fail(c, "out of device memory (%s, %zu bytes)", name, bytes);
-  if (bytes) HIPCHK(c, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-  *dst = static_cast<const T *>(p);
   return 0;
 }
 
@@ -7116,17 +7197,7 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   lb.doc_offsets = mo;
   lb.key_bits = h.key_bits;
   cw_list_result lr = W;
-  if (!dev) {
-    lr.weave_perm = scratch_t<uint32_t>(c, "g_perm", NCs);
-    lr.visible_bits = W.visible_bits ? scratch_t<uint32_t>(c, "g_bits", (NCs + 31) / 32) : nullptr;
-    lr.visible_count = scratch_t<uint32_t>(c, "g_vc", D + 1);
-    lr.max_ts = W.max_ts ? scratch_t<uint64_t>(c, "g_mts", D + 1) : nullptr;
-    lr.status = scratch_t<uint32_t>(c, "g_st", D + 1);
-    lr.yarn_perm = W.yarn_perm ? scratch_t<uint32_t>(c, "g_yarn", NCs) : nullptr;
-    if (!lr.weave_perm || !lr.visible_count || !lr.status || (W.visible_bits && !lr.visible_bits) ||
-        (W.max_ts && !lr.max_ts) || (W.yarn_perm && !lr.yarn_perm))
-      return fail(c, "out of device memory (merge outputs)");
-  }
+  if (!dev && stage_list_result(c, W, NC, D, &lr)) return -1;
   if (weave_lists_device(c, &lb, h.mid, h.mca, h.mkd, &lr)) return -1;
   if (exact_fixup(c, &lb, h.mid, h.mca, h.mkd, &lr, c->x_hint)) return -1;
   // the union's DUP and the merged-empty documents' ROOT join the weave's bits
@@ -7140,19 +7211,11 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   if (!dev) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipMemcpy(res->merged_src, h.msrc, NM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(W.weave_perm, lr.weave_perm, NM * 4, hipMemcpyDeviceToHost));
-    if (W.visible_bits)
-      HIPCHK(c, hipMemcpy(W.visible_bits, lr.visible_bits, (NM + 31) / 32 * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(W.visible_count, lr.visible_count, D * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(W.status, lr.status, D * 4, hipMemcpyDeviceToHost));
-    if (W.max_ts) HIPCHK(c, hipMemcpy(W.max_ts, lr.max_ts, D * 8, hipMemcpyDeviceToHost));
-    if (W.yarn_perm) HIPCHK(c, hipMemcpy(W.yarn_perm, lr.yarn_perm, NM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipDeviceSynchronize());
+    if (unstage_list_result(c, lr, NM, D, W)) return -1;
   } else if (!c->async) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  if (c->prof) return collect_prof(c);
-  return 0;
+  return c->prof ? collect_prof(c) : 0;
 }
 
 // cw_merge_maps: uploads (host memspace), the union stage (mapmerge.hip), one
@@ -7256,8 +7319,7 @@ int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result
   } else if (!c->async) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
-  if (c->prof) return collect_prof(c);
-  return 0;
+  return c->prof ? collect_prof(c) : 0;
 }
 
 int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int memspace) {
@@ -7266,25 +7328,19 @@ int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int
   const cw_list_batch &L = bt->nodes;
   const uint64_t D = L.n_docs;
   const uint64_t *off = L.doc_offsets;
-  if (!off || off[0] != 0) return fail(c, "doc_offsets must start at 0");
+  // (no per-document limit beyond the batch's)
+  if (check_doc_offsets(c, off, D, 0, 0)) return -1;
   if (L.site_bits == 0 || L.site_bits > 10) return fail(c, "weft needs site_bits in 1..10");
   if (!bt->cut) return fail(c, "cut is required");
   const uint64_t N = off[D];
-  if (N >= 0xFFFFFFFFull) return fail(c, "batch too large");
   cw_list_result &W = res->weave;
   if (!res->kept_offsets || !res->kept_src || !W.weave_perm || !W.visible_count || !W.status)
     return fail(c, "kept_offsets, kept_src, weave_perm, visible_count and status are required");
-  std::vector<uint32_t> h_off(D + 1);
-  for (uint64_t d = 0; d <= D; d++) {
-    if (d < D && off[d + 1] < off[d]) return fail(c, "doc_offsets not monotone");
-    h_off[d] = (uint32_t)off[d];
-  }
+  const std::vector<uint32_t> h_off(off, off + D + 1);
   HIPCHK(c, hipSetDevice(c->device));
   const size_t Ns = std::max<uint64_t>(N, 1), NC = (size_t)D << L.site_bits;
-  uint64_t *id = scratch_t<uint64_t>(c, "w_id", Ns), *ca = scratch_t<uint64_t>(c, "w_ca", Ns);
-  uint8_t *kd = scratch_t<uint8_t>(c, "w_kd", Ns);
-  uint64_t *cut = scratch_t<uint64_t>(c, "w_cut", std::max<size_t>(NC, 1));
-  uint32_t *doff = scratch_t<uint32_t>(c, "w_off", D + 1), *koff = scratch_t<uint32_t>(c, "w_koff", D + 1);
+  if (N && (!L.id_key || !L.cause_key || !L.kind)) return fail(c, "null input arrays");
+  uint32_t *koff = scratch_t<uint32_t>(c, "w_koff", D + 1);
   uint32_t *kcnt = scratch_t<uint32_t>(c, "w_kcnt", D + 1), *kst = scratch_t<uint32_t>(c, "w_kst", D + 1);
   // kept nodes: at most the document's nodes plus one [id] node per named site
   const size_t NKcap = Ns + NC;
@@ -7292,18 +7348,17 @@ int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int
   uint64_t *kid = scratch_t<uint64_t>(c, "w_kid", NKcap), *kca = scratch_t<uint64_t>(c, "w_kca", NKcap);
   uint8_t *kkd = scratch_t<uint8_t>(c, "w_kkd", NKcap);
   uint32_t *ksrc = scratch_t<uint32_t>(c, "w_ksrc", NKcap);
-  if (!id || !ca || !kd || !cut || !doff || !koff || !kcnt || !kst || !kid || !kca || !kkd || !ksrc)
+  if (!koff || !kcnt || !kst || !kid || !kca || !kkd || !ksrc)
     return fail(c, "out of device memory (weft)");
   if (!grid_ok(D, 1024)) return fail(c, "batch too large for one dispatch");
+  const uint64_t *id, *ca, *cut;
+  const uint8_t *kd;
+  const uint32_t *doff;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (N) {
-    if (!L.id_key || !L.cause_key || !L.kind) return fail(c, "null input arrays");
-    HIPCHK(c, hipMemcpy(id, L.id_key, N * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(ca, L.cause_key, N * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(kd, L.kind, N, hipMemcpyHostToDevice));
-  }
-  if (NC) HIPCHK(c, hipMemcpy(cut, bt->cut, NC * 8, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(doff, h_off.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  if (upload(c, "w_id", L.id_key, N * 8, &id) || upload(c, "w_ca", L.cause_key, N * 8, &ca) ||
+      upload(c, "w_kd", L.kind, N, &kd) || upload(c, "w_cut", bt->cut, NC * 8, &cut) ||
+      upload(c, "w_off", h_off.data(), (D + 1) * 4, &doff))
+    return -1;
   uint64_t *ko = res->kept_offsets;
   ko[0] = 0;
   if (D == 0) return 0;
@@ -7326,38 +7381,17 @@ int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int
   if (ensure_tables(c, D, ko)) return -1;
   cw_list_batch lb = L;
   lb.doc_offsets = ko;
-  const size_t NKs = std::max<uint64_t>(NK, 1);
-  cw_list_result lr{};
-  lr.weave_perm = scratch_t<uint32_t>(c, "w_perm", NKs);
-  lr.visible_bits = W.visible_bits ? scratch_t<uint32_t>(c, "w_bits", (NKs + 31) / 32) : nullptr;
-  lr.visible_count = scratch_t<uint32_t>(c, "w_vc", D + 1);
-  lr.max_ts = W.max_ts ? scratch_t<uint64_t>(c, "w_mts", D + 1) : nullptr;
-  lr.status = scratch_t<uint32_t>(c, "w_st", D + 1);
-  lr.yarn_perm = W.yarn_perm ? scratch_t<uint32_t>(c, "w_yarn", NKs) : nullptr;
-  if (!lr.weave_perm || !lr.visible_count || !lr.status || (W.visible_bits && !lr.visible_bits) ||
-      (W.max_ts && !lr.max_ts) || (W.yarn_perm && !lr.yarn_perm))
-    return fail(c, "out of device memory (weft outputs)");
+  cw_list_result lr;
+  if (stage_list_result(c, W, NK, D, &lr)) return -1;
   if (weave_lists_device(c, &lb, kid, kca, kkd, &lr)) return -1;
   if (exact_fixup(c, &lb, kid, kca, kkd, &lr, c->x_hint)) return -1;
   hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, kst,
                      lr.status, (uint32_t)D);
   if (check_launch(c, "or_status")) return -1;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (NK) {
-    HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(W.weave_perm, lr.weave_perm, NK * 4, hipMemcpyDeviceToHost));
-    if (W.visible_bits)
-      HIPCHK(c, hipMemcpy(W.visible_bits, lr.visible_bits, (NK + 31) / 32 * 4, hipMemcpyDeviceToHost));
-    if (W.yarn_perm) HIPCHK(c, hipMemcpy(W.yarn_perm, lr.yarn_perm, NK * 4, hipMemcpyDeviceToHost));
-  }
-  HIPCHK(c, hipMemcpy(W.visible_count, lr.visible_count, D * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(W.status, lr.status, D * 4, hipMemcpyDeviceToHost));
-  if (W.max_ts) HIPCHK(c, hipMemcpy(W.max_ts, lr.max_ts, D * 8, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipDeviceSynchronize());
-  for (uint64_t d = 0; d < D; d++)
-    if (ko[d + 1] == ko[d]) W.status[d] |= CW_STATUS_ROOT;
-  if (c->prof) return collect_prof(c);
-  return 0;
+  if (NK) HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
+  if (unstage_list_result(c, lr, NK, D, W) || root_empty_docs(c, ko, D, W.status, false)) return -1;
+  return c->prof ? collect_prof(c) : 0;
 }
 
 }  // namespace

@@ -1272,7 +1272,6 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
            *sub_off = dev_tab(c, "t_doc_off");
   const dim3 B256(256), GF((F + 63) / 64), B64(64);
   const uint32_t T = c->tab.T;
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
   std::vector<uint8_t> h_early(F), run(F, 0), x2(F, 0);
   std::vector<uint32_t> h_app(F);
   HIPCHK(c, hipMemcpyAsync(h_early.data(), dearly, F, hipMemcpyDeviceToHost, c->stream));
@@ -1535,10 +1534,11 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
         HIPCHK(c, hipMemsetAsync(moved, 0, F, c->stream));
         if (positions2(0, p2B, p2A)) return -1;
         std::swap(p2A, p2B);
-        HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 8, hipMemcpyDeviceToHost, c->stream));
+        const uint32_t *pc = read_small(c, ctl, 8, NO_WAIT);
+        if (!pc) return -1;
         HIPCHK(c, hipMemcpyAsync(h_moved.data(), moved, F, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->pin_small[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", c->pin_small[1]);
+        if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
         bool more = false;
         for (uint32_t f = 0; f < F; f++) {
           only[f] = only[f] && h_moved[f];  // a document that reproduced its weave is done
@@ -1566,9 +1566,9 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
       }
       if (check_launch(c, "xsyn_compact")) return -1;
     }
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->pin_small[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", c->pin_small[1]);
+    const uint32_t *pc = read_small(c, ctl, 8);
+    if (!pc) return -1;
+    if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
     hipLaunchKernelGGL(k_xsyn_zero, GF, B64, 0, c->stream, d_sb, F, d_odoc, out->visible_count);
     for (uint32_t adj = 0; adj < (any_x2 ? 2u : 1u); adj++) {
       Launch L(c, "xsyn_emit", (double)NX * (4 + 4 + 4 + 1) + (double)NX / 8);
@@ -1645,7 +1645,8 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
   const uint64_t D = bt->n_docs;
   const uint64_t *off = bt->doc_offsets;
   if (!hint || D == 0 || off[D] == 0) return 0;
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
+  constexpr uint64_t FEW_DOCS = 16;  // their status words fit the small readback
+  static_assert(FEW_DOCS * 4 <= PIN_SMALL_BYTES, "exact_fixup: FEW_DOCS status words in one read_small");
   if (D == 1 && c->x_pending && bt->key_bits && bt->key_bits < 64) {
     // one giant list: its status was copied out after the front end (KEY_RANGE,
     // set later, needs key_bits >= 64); wait for that copy, not for the stream
@@ -1653,13 +1654,13 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
     const uint32_t st = c->pin_status[0];
     if (!(st & X_MASK) || (st & X_SKIP)) return 0;
     if (c->xfront.ok && c->xfront.n == off[1]) return exact_giant_front(c, bt, out);
-  } else if (D <= 16) {
+  } else if (D <= FEW_DOCS) {
     // a few documents: their status words in one readback
-    HIPCHK(c, hipMemcpyAsync(c->pin_small, out->status, D * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t *st = read_small(c, out->status, D * 4);
+    if (!st) return -1;
     bool any = false;
     for (uint64_t d = 0; d < D; d++)
-      any |= (c->pin_small[d] & X_MASK) && !(c->pin_small[d] & X_SKIP) && off[d + 1] > off[d];
+      any |= (st[d] & X_MASK) && !(st[d] & X_SKIP) && off[d + 1] > off[d];
     if (!any) return 0;
   }
   uint32_t *cnt = scratch_t<uint32_t>(c, "x_cnt", 1);
@@ -1675,9 +1676,9 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
   hipLaunchKernelGGL(k_xcount, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream,
                      out->status, doff, (uint32_t)D, cnt);
   if (check_launch(c, "xcount")) return -1;
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, cnt, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pin_small[0] == 0) return 0;
+  const uint32_t *pcnt = read_small(c, cnt, 4);
+  if (!pcnt) return -1;
+  if (pcnt[0] == 0) return 0;
   // which documents
   std::vector<uint32_t> st(D);
   HIPCHK(c, hipMemcpy(st.data(), out->status, D * 4, hipMemcpyDeviceToHost));

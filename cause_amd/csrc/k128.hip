@@ -106,49 +106,26 @@ int weave_lists_k128_impl(cw_ctx *c, const cw_list_batch_k128 *bt, cw_list_resul
   if (!bt || !res) return fail(c, "null batch/result");
   const uint64_t D = bt->n_docs;
   const uint64_t *off = bt->doc_offsets;
-  if (!off || off[0] != 0) return fail(c, "doc_offsets must start at 0");
-  const uint64_t N64 = off[D];
-  if (N64 >= 0xFFFFFFFFull) return fail(c, "batch too large: N=%llu", (unsigned long long)N64);
-  uint64_t nmax = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    if (off[d + 1] < off[d]) return fail(c, "doc_offsets not monotone");
-    nmax = std::max(nmax, off[d + 1] - off[d]);
-    if (D == 1 ? off[1] >= SUCCW_END : off[d + 1] - off[d] >= LINK_IDX)
-      return fail(c, "document %llu too large", (unsigned long long)d);
-  }
+  uint64_t nmax;
+  if (check_doc_offsets(c, off, D, SUCCW_END, LINK_IDX, &nmax)) return -1;
   if (!res->weave_perm || !res->visible_count || !res->status)
     return fail(c, "weave_perm, visible_count and status are required");
   if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
-  const uint32_t N = (uint32_t)N64;
+  const bool host = memspace == CW_MEM_HOST;
+  const uint32_t N = (uint32_t)off[D];
   HIPCHK(c, hipSetDevice(c->device));
   const size_t Ns = std::max<uint32_t>(N, 1);
   // device copies of the inputs (host memory) and of the outputs
   const uint64_t *id2 = bt->id_key, *ca2 = bt->cause_key;
   const uint8_t *kind = bt->kind;
   cw_list_result dres = *res;
-  if (memspace == CW_MEM_HOST) {
+  if (host) {
     if (N && (!id2 || !ca2 || !kind)) return fail(c, "null input arrays");
-    uint64_t *did = scratch_t<uint64_t>(c, "h_id", 2 * Ns), *dca = scratch_t<uint64_t>(c, "h_cause", 2 * Ns);
-    uint8_t *dk = scratch_t<uint8_t>(c, "h_kind", Ns);
-    dres.weave_perm = scratch_t<uint32_t>(c, "h_perm", Ns);
-    dres.visible_bits = res->visible_bits ? scratch_t<uint32_t>(c, "h_bits", (Ns + 31) / 32) : nullptr;
-    dres.visible_count = scratch_t<uint32_t>(c, "h_vcount", D + 1);
-    dres.max_ts = res->max_ts ? scratch_t<uint64_t>(c, "h_maxts", D + 1) : nullptr;
-    dres.status = scratch_t<uint32_t>(c, "h_status", D + 1);
-    dres.yarn_perm = res->yarn_perm ? scratch_t<uint32_t>(c, "h_yarn", Ns) : nullptr;
-    if (!did || !dca || !dk || !dres.weave_perm || !dres.visible_count || !dres.status ||
-        (res->visible_bits && !dres.visible_bits) || (res->max_ts && !dres.max_ts) ||
-        (res->yarn_perm && !dres.yarn_perm))
-      return fail(c, "out of device memory (host-mode staging)");
+    if (stage_list_result(c, *res, N, D, &dres)) return -1;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (N) {
-      HIPCHK(c, hipMemcpy(did, id2, (size_t)N * 16, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dca, ca2, (size_t)N * 16, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dk, kind, N, hipMemcpyHostToDevice));
-    }
-    id2 = did;
-    ca2 = dca;
-    kind = dk;
+    if (upload(c, "h_id", id2, (size_t)N * 16, &id2) || upload(c, "h_cause", ca2, (size_t)N * 16, &ca2) ||
+        upload(c, "h_kind", kind, N, &kind))
+      return -1;
   }
   uint64_t *rid = scratch_t<uint64_t>(c, "k128_rid", Ns), *rca = scratch_t<uint64_t>(c, "k128_rca", Ns);
   if (!rid || !rca) return fail(c, "out of device memory (k128)");
@@ -240,30 +217,13 @@ int weave_lists_k128_impl(cw_ctx *c, const cw_list_batch_k128 *bt, cw_list_resul
       return -1;
     HIPCHK(c, hipMemcpyAsync(dres.yarn_perm, vo, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
   }
-  if (memspace == CW_MEM_HOST) {
+  if (host) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (N) {
-      HIPCHK(c, hipMemcpy(res->weave_perm, dres.weave_perm, (size_t)N * 4, hipMemcpyDeviceToHost));
-      if (res->visible_bits)
-        HIPCHK(c, hipMemcpy(res->visible_bits, dres.visible_bits, ((size_t)N + 31) / 32 * 4,
-                            hipMemcpyDeviceToHost));
-      if (res->yarn_perm)
-        HIPCHK(c, hipMemcpy(res->yarn_perm, dres.yarn_perm, (size_t)N * 4, hipMemcpyDeviceToHost));
-    }
-    HIPCHK(c, hipMemcpy(res->visible_count, dres.visible_count, D * 4, hipMemcpyDeviceToHost));
-    if (res->max_ts) HIPCHK(c, hipMemcpy(res->max_ts, dres.max_ts, D * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->status, dres.status, D * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipDeviceSynchronize());
-    for (uint64_t d = 0; d < D; d++)
-      if (off[d + 1] == off[d]) res->status[d] |= CW_STATUS_ROOT;
-  } else {
-    for (uint64_t d = 0; d < D; d++)
-      if (off[d + 1] == off[d])
-        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(res->status + d), CW_STATUS_ROOT, 1, c->stream));
-    if (!c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (unstage_list_result(c, dres, N, D, *res)) return -1;
   }
-  if (c->prof) return collect_prof(c);
-  return 0;
+  if (root_empty_docs(c, off, D, res->status, !host)) return -1;
+  if (!host && !c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
+  return c->prof ? collect_prof(c) : 0;
 }
 
 }  // namespace

@@ -284,11 +284,11 @@ namespace {
 // bytes: none then, else out_bytes more per merged node.
 int fused_union_tail(cw_ctx *c, size_t rec, const uint32_t *ctl, const uint64_t *dmo, uint64_t *mo,
                      uint64_t D, double out_bytes) {
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 4, hipMemcpyDeviceToHost, c->stream));
+  const uint32_t *pc = read_small(c, ctl, 4, NO_WAIT);
+  if (!pc) return -1;
   HIPCHK(c, hipMemcpyAsync(mo, dmo, (D + 1) * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const bool bail = c->pin_small[0] != 0;
+  const bool bail = pc[0] != 0;
   if (rec < c->pending.size()) c->pending[rec].bytes = bail ? 0 : c->pending[rec].bytes + (double)mo[D] * out_bytes;
   return bail;
 }

@@ -793,12 +793,11 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
   if (pc.verify &&
       memcmp(pc.off.data(), off, (D + 1) * 8) != 0)  // (the kernel runs meanwhile)
     return 2;  // another layout after all: the caller checks it and weaves again
-  if (!c->pin_small) HIPCHK(c, hipHostMalloc((void **)&c->pin_small, 64, hipHostMallocDefault));
-  HIPCHK(c, hipMemcpyAsync(c->pin_small, ctl, 12, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (c->pin_small[2]) return 1;  // a pack's keys need more than 63 bits: the general path
-  const uint64_t S = c->pin_small[0];
-  if (c->pin_small[1]) return fail(c, "cap_segs too small: %llu key weaves", (unsigned long long)S);
+  const uint32_t *pc3 = read_small(c, ctl, 12);
+  if (!pc3) return -1;
+  if (pc3[2]) return 1;  // a pack's keys need more than 63 bits: the general path
+  const uint64_t S = pc3[0];
+  if (pc3[1]) return fail(c, "cap_segs too small: %llu key weaves", (unsigned long long)S);
   if (tprof) {
     double a[8];
     if (read_stamps(c, tprof, P, 8, 8, a)) return -1;
