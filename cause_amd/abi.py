@@ -109,6 +109,16 @@ class CwWeftResult(C.Structure):
                 ("weave", CwListResult)]
 
 
+class CwMapWeftBatch(C.Structure):
+    _fields_ = [("nodes", CwMapBatch), ("site_shift", C.c_uint32), ("site_bits", C.c_uint32),
+                ("cut", C.c_void_p)]
+
+
+class CwMapWeftResult(C.Structure):
+    _fields_ = [("kept_offsets", C.POINTER(C.c_uint64)), ("kept_src", C.c_void_p),
+                ("maps", CwMapResult)]
+
+
 class CwRankedList(C.Structure):
     _fields_ = [("n", C.c_uint64), ("par", C.c_void_p), ("kind", C.c_void_p), ("val", C.c_void_p)]
 
@@ -220,6 +230,10 @@ def lib():
         L.cw_weft_lists.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch), C.POINTER(CwWeftResult),
                                     C.c_int]
         L.cw_weft_lists.restype = C.c_int
+        if hasattr(L, "cw_weft_maps"):  # (a build from before it, named by CW_LIB for an A/B run)
+            L.cw_weft_maps.argtypes = [C.c_void_p, C.POINTER(CwMapWeftBatch),
+                                       C.POINTER(CwMapWeftResult), C.c_int]
+            L.cw_weft_maps.restype = C.c_int
         P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
         L.cw_sort_keys.argtypes = [P, P, U64, U32, P, P]
         L.cw_lookup_keys.argtypes = [P, P, U64, P, U64, U32, P, P]
@@ -294,6 +308,14 @@ class MapMergeResult:
     """Union of two node bags per collection and its map weave (cw_merge_maps)."""
     offsets: np.ndarray      # uint64[D+1] merged collections
     src: np.ndarray          # uint32[M] merged nodes in id order: < na_d -> a, else b (- na_d)
+    maps: MapResult          # every index is collection-local into src
+
+
+@dataclass
+class MapWeftResult:
+    """Kept nodes per collection and their map weave (cw_weft_maps)."""
+    offsets: np.ndarray      # uint64[D+1] kept collections
+    src: np.ndarray          # uint32[M] kept nodes in input order, then UINT32_MAX per [id] node
     maps: MapResult          # every index is collection-local into src
 
 
@@ -775,5 +797,62 @@ class Weaver:
                     "cw_merge_maps")
         S, M = int(r.maps.n_segs), int(mo[-1])
         return MapMergeResult(mo, src[:M], MapResult(
+            out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
+            out.seg_perm[:M + S], out.status[:D]))
+
+    def weft_maps_device(self, offsets, ptrs, token_bits, key_bits, site_shift, site_bits, cut_ptr,
+                         src_ptr, out_ptrs, cap_segs):
+        """Device-memory call of cw_weft_maps.  ptrs = (id_key, cause, cause_is_id,
+        kind) device pointers; cut_ptr: the cut table (uint64[D << site_bits]) in
+        device memory; src_ptr: kept_src (uint32[N + (D << site_bits)]); out_ptrs
+        as weave_maps_device (seg_perm sized N + (D << site_bits) + cap_segs).
+        Returns (kept offsets uint64[D+1], n_segs)."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        vp = lambda p: C.c_void_p(p) if p else None
+        wb = CwMapWeftBatch(self._map_batch(off, [vp(p) for p in ptrs], key_bits, token_bits),
+                            site_shift, site_bits, vp(cut_ptr))
+        ko = np.zeros(len(off), np.uint64)
+        g = lambda n: C.c_void_p(out_ptrs[n])
+        r = CwMapWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
+                            CwMapResult(cap_segs, 0, g("seg_offsets"), g("seg_coll"), g("seg_key"),
+                                        g("seg_active"), g("seg_perm"), g("status")))
+        self._check(self._L.cw_weft_maps(self._h, C.byref(wb), C.byref(r), CW_MEM_DEVICE),
+                    "cw_weft_maps")
+        return ko, int(r.maps.n_segs)
+
+    def weft_maps(self, offsets, id_key, cause, cause_is_id, kind, token_bits, site_shift,
+                  site_bits, cut, key_bits=0) -> MapWeftResult:
+        """Host-memory call of cw_weft_maps.  cut: uint64[D << site_bits] packed
+        cut id per (collection, site rank), 0 = site not named.  Returns the kept
+        nodes (src = collection-local input index, input order, then UINT32_MAX
+        per [id] node) and their map weave."""
+        i = np.ascontiguousarray(id_key, np.uint64)
+        c = np.ascontiguousarray(cause, np.uint64)
+        ci = np.ascontiguousarray(cause_is_id, np.uint8)
+        k = np.ascontiguousarray(kind, np.uint8)
+        off = np.ascontiguousarray(offsets, np.uint64)
+        cut = np.ascontiguousarray(cut, np.uint64)
+        D, N = len(off) - 1, len(i)
+        if int(off[-1]) != N or len({len(x) for x in (i, c, ci, k)}) != 1:
+            raise ValueError("offsets[-1] != number of nodes")
+        if 1 <= site_bits <= 10 and len(cut) != D << site_bits:  # (else: the library's error)
+            raise ValueError("cut size != collections << site_bits")
+        wb = CwMapWeftBatch(self._map_batch(off, [_ptr(x) for x in (i, c, ci, k)], key_bits,
+                                            token_bits), site_shift, site_bits, _ptr(cut))
+        ko = np.zeros(D + 1, np.uint64)
+        NK = N + (D << site_bits)  # + one [id] node per named site
+        cap = max(NK, 1)
+        src = np.zeros(cap, np.uint32)
+        out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
+                        np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
+                        np.zeros(NK + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
+        r = CwMapWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
+                            CwMapResult(cap, 0, _ptr(out.seg_offsets), _ptr(out.seg_coll),
+                                        _ptr(out.seg_key), _ptr(out.seg_active),
+                                        _ptr(out.seg_perm), _ptr(out.status)))
+        self._check(self._L.cw_weft_maps(self._h, C.byref(wb), C.byref(r), CW_MEM_HOST),
+                    "cw_weft_maps")
+        S, M = int(r.maps.n_segs), int(ko[-1])
+        return MapWeftResult(ko, src[:M], MapResult(
             out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
             out.seg_perm[:M + S], out.status[:D]))

@@ -11,6 +11,7 @@ order equals the full reweave).  There is no CPU weave in this module.
     shared.cljc:300-314   merge-trees               -> merge_trees / merge_lists (cw_merge_lists)
     map.cljc:248-249      causal-merge              -> merge_trees / merge_maps (cw_merge_maps)
     shared.cljc:268-293   weft                      -> weft / weft_lists (cw_weft_lists)
+    map.cljc:246-247      weft (maps)               -> map_weft / weft_maps (cw_weft_maps)
     shared.cljc:259-266   refresh-caches            -> refresh_caches
     list.cljc:20-34       weave (all arities)       -> list_weave / weave_lists
     list.cljc:36-43       conj- / cons-             -> list_conj / list_cons
@@ -490,6 +491,66 @@ def merge_maps(pairs):
         new["lamport_ts"] = max([ct1["lamport_ts"]] + fresh)
         out.append(new)
     return out
+
+
+def weft_maps(items):
+    """CausalMap's weft (map.cljc:246-247: s/weft, shared.cljc:268-293, with the
+    map weave) for many (map ct, ids-to-cut-yarns) pairs in ONE GPU call
+    (cw_weft_maps): time travel to the cut, then the full map reweave.  A cut id
+    that is not a node keeps its site's whole yarn plus the one-element node
+    ``(id,)`` (body ``()`` in ``nodes``), last in that yarn and woven as
+    ``(id, ROOT_ID, None)`` under the nil key (map.cljc:30)."""
+    docs = [[(i, b[0], b[1]) for i, b in ct["nodes"].items()] for ct, _ in items]
+    cuts = []
+    for ct, ids in items:
+        last = {}
+        for i in ids:  # (assoc-in [::yarns site] ..): the last id of a site wins
+            if i != ROOT_ID:
+                last[i[1]] = i
+        cuts.append(last)
+    pm = pack.pack_maps(docs, extra_ids=[list(c.values()) for c in cuts],
+                        min_site_bits=1)  # cw_weft_maps indexes cuts by site rank
+    lay = pm.layout
+    S = 1 << lay.site_bits
+    cut = np.zeros(len(items) << lay.site_bits, np.uint64)
+    for d, (last, rank) in enumerate(zip(cuts, pm.ranks)):
+        for site, i in last.items():
+            word = lay.pack(i[0], rank[site], i[2])
+            if word == 0:  # (0 = site not named: only an id sorting at the root id packs so)
+                raise pack.KeyRangeError(f"cut id {i} sorts at the root id")
+            cut[d * S + rank[site]] = word
+    res = weaver().weft_maps(pm.offsets, pm.id_key, pm.cause, pm.cause_is_id, pm.kind,
+                             pm.token_bits, lay.site_shift, lay.site_bits, cut, lay.key_bits)
+    segs_of = _segs_by_coll(res.maps)
+    out = []
+    for d, ((ct, ids), nodes, last) in enumerate(zip(items, docs, cuts)):
+        st = int(res.maps.status[d])
+        if st & (abi.STATUS_DUP | abi.STATUS_MAP_KEY | abi.STATUS_INTERNAL):
+            raise CauseError(f"weft outside the weave's domain (status {st})", {"weave-domain"})
+        lo, hi = int(res.offsets[d]), int(res.offsets[d + 1])
+        # the [id] nodes come after the kept nodes, in site-rank order; woven
+        # they destructure to cause nil, value nil
+        bogus = iter(sorted((i for i in last.values() if i not in ct["nodes"]),
+                            key=lambda i: pm.ranks[d][i[1]]))
+        kept = [nodes[s] if s != 0xFFFFFFFF else (next(bogus), None, None)
+                for s in res.src[lo:hi].tolist()]
+        is_bogus = [s == 0xFFFFFFFF for s in res.src[lo:hi].tolist()]
+        new = new_map_ct(site_id=ct["site_id"], uuid=ct["uuid"])
+        new["nodes"] = {n[0]: () if b else (n[1], n[2]) for n, b in zip(kept, is_bogus)}
+        new["weave"], new["_active"] = _key_weaves(res.maps, segs_of.get(d, []), kept, pm, d)
+        yarns = {}
+        # yarns on the host: id order, (conj yarn-prefix [id]) puts the [id] node last
+        for n, b in sorted(zip(kept, is_bogus), key=lambda t: (t[1], t[0][0][0], t[0][0][2])):
+            yarns.setdefault(n[0][1], []).append((n[0],) if b else n)
+        new["yarns"] = yarns
+        new["lamport_ts"] = max(i[0] for i in ids if i != ROOT_ID)
+        out.append(new)
+    return out
+
+
+def map_weft(ct, ids):
+    """(c/weft causal-map ids) -- map.cljc:246-247 over shared.cljc:268-293."""
+    return weft_maps([(ct, ids)])[0]
 
 
 def map_insert_bulk(ct, nodes):

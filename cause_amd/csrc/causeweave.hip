@@ -4496,6 +4496,14 @@ struct cw_ctx {
     LookBack lb;                   // k_map_union's look-back words
     bool ok = false;
   } mmerge;
+  uint32_t map_weft_fused = 1;     // map_weft_fused: one-kernel select stage of cw_weft_maps
+  struct MapWeft {                 // k_map_weft's pack table, cached by the layout and site_bits
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> doc0;
+    uint32_t site_bits = 0, pk = 0, dmax = 1;
+    LookBack lb;                   // k_map_weft's look-back words
+    bool ok = false;
+  } mweft;
   uint32_t list_merge_fused = 1;   // list_merge_fused: one-kernel union stage of cw_merge_lists
   struct ListMerge {               // the two layouts of the last cw_merge_lists call, as uploaded
     std::vector<uint64_t> ao, bo;
@@ -6114,6 +6122,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "exact.hip"
 #include "mappack.hip"
 #include "mapmerge.hip"
+#include "mapweft.hip"
 #include "listmerge.hip"
 #include "dist.hip"
 
@@ -7322,6 +7331,111 @@ int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result
   return c->prof ? collect_prof(c) : 0;
 }
 
+// cw_weft_maps: uploads (host memspace), the select stage (mapweft.hip), one
+// device-to-host copy of the kept offsets, weave_maps_impl in device memspace
+// on the kept arrays, the WEFT bits, copies out.  The kept arrays have scratch
+// names of their own (mw_*): weave_maps_impl reuses skA / svA / m_* and the sort's.
+int weft_maps_impl(cw_ctx *c, const cw_map_weft_batch *bt, cw_map_weft_result *res, int memspace) {
+  if (!bt || !res) return fail(c, "null batch/result");
+  if (memspace != CW_MEM_HOST && memspace != CW_MEM_DEVICE) return fail(c, "bad memspace");
+  const bool dev = memspace == CW_MEM_DEVICE;
+  const cw_map_batch &B = bt->nodes;
+  const uint64_t D = B.n_colls, *off = B.coll_offsets;
+  if (!off) return fail(c, "coll_offsets is required (host memory)");
+  if (off[0] != 0) return fail(c, "coll_offsets[0] must be 0");
+  for (uint64_t d = 0; d < D; d++)
+    if (off[d + 1] < off[d]) return fail(c, "coll_offsets not monotone");
+  const uint32_t sb = bt->site_bits;
+  if (sb == 0 || sb > 10) return fail(c, "weft needs site_bits in 1..10");
+  if (bt->site_shift + sb > 64) return fail(c, "site_shift + site_bits must be <= 64");
+  if (!bt->cut) return fail(c, "cut is required");
+  cw_map_result &M = res->maps;
+  if (!res->kept_offsets || !res->kept_src || !M.seg_offsets || !M.seg_coll || !M.seg_key ||
+      !M.seg_active || !M.seg_perm || !M.status)
+    return fail(c, "kept_offsets, kept_src and every cw_map_result array are required");
+  if (B.token_bits == 0 || B.token_bits > 62) return fail(c, "token_bits must be 1..62");
+  const uint64_t N = off[D], NS = D << sb;
+  // kept nodes: at most the collection's nodes plus one [id] node per site rank
+  if (N + NS >= 0xFFFFFFFFull)
+    return fail(c, "weft too large: %llu nodes and cut slots (limit 2^32-2)", (unsigned long long)(N + NS));
+  if (N && (!B.id_key || !B.cause || !B.cause_is_id || !B.kind)) return fail(c, "null input arrays");
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint64_t cap = M.cap_segs;
+  uint64_t *ko = res->kept_offsets;
+  MwHost h{};
+  h.D = D;
+  h.N = N;
+  h.off = off;
+  h.in = MwIn{B.id_key, B.cause, B.cause_is_id, B.kind, nullptr, bt->cut, bt->site_shift, sb};
+  if (!dev && D) {  // uploads
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (upload(c, "mw_id", B.id_key, N * 8, &h.in.id) || upload(c, "mw_ca", B.cause, N * 8, &h.in.cause) ||
+        upload(c, "mw_cis", B.cause_is_id, N, &h.in.cis) || upload(c, "mw_kd", B.kind, N, &h.in.kind) ||
+        upload(c, "mw_cut", bt->cut, NS * 8, &h.in.cut))
+      return -1;
+  }
+  // the kept collections (device) and the WEFT words
+  const uint64_t NKcap = N + NS;
+  uint64_t *kid = scratch_t<uint64_t>(c, "mw_kid", NKcap), *kca = scratch_t<uint64_t>(c, "mw_kca", NKcap);
+  uint8_t *kcis = scratch_t<uint8_t>(c, "mw_kcis", NKcap), *kkd = scratch_t<uint8_t>(c, "mw_kkd", NKcap);
+  uint32_t *ksrc = dev ? res->kept_src : scratch_t<uint32_t>(c, "mw_ksrc", NKcap);
+  uint32_t *wst = scratch_t<uint32_t>(c, "mw_weft", D);
+  if (!kid || !kca || !kcis || !kkd || !ksrc || !wst)
+    return fail(c, "out of device memory (map weft, N=%llu)", (unsigned long long)NKcap);
+  h.out = MwOut{kid, kca, kcis, kkd, ksrc, nullptr, wst};
+  if (D == 0) {
+    ko[0] = 0;
+  } else {
+    int rc = 1;
+    if (c->map_weft_fused) rc = map_weft_fused(c, h, ko);
+    if (rc == 1) rc = map_weft_general(c, h, ko);  // one oversize collection: the whole call
+    if (rc) return -1;
+  }
+  const uint64_t NK = ko[D];
+  // the map reweave of the kept collections, in device memory
+  cw_map_batch mb{};
+  mb.n_colls = D;
+  mb.coll_offsets = ko;
+  mb.id_key = kid;
+  mb.cause = kca;
+  mb.cause_is_id = kcis;
+  mb.kind = kkd;
+  mb.key_bits = B.key_bits;
+  mb.token_bits = B.token_bits;
+  cw_map_result mr = M;
+  if (!dev) {
+    mr.seg_offsets = scratch_t<uint64_t>(c, "mw_so", cap + 1);
+    mr.seg_coll = scratch_t<uint32_t>(c, "mw_sc", cap);
+    mr.seg_key = scratch_t<uint64_t>(c, "mw_sk", cap);
+    mr.seg_active = scratch_t<int64_t>(c, "mw_sa", cap);
+    mr.seg_perm = scratch_t<uint32_t>(c, "mw_sp", NK + cap);
+    mr.status = scratch_t<uint32_t>(c, "mw_st", D);
+    if (!mr.seg_offsets || !mr.seg_coll || !mr.seg_key || !mr.seg_active || !mr.seg_perm || !mr.status)
+      return fail(c, "out of device memory (map weft outputs)");
+  }
+  if (weave_maps_impl(c, &mb, &mr, CW_MEM_DEVICE)) return -1;
+  M.n_segs = mr.n_segs;
+  if (D) {  // the collections that got an [id] node: WEFT joins the weave's bits
+    hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, wst,
+                       mr.status, (uint32_t)D);
+    if (check_launch(c, "or_status")) return -1;
+  }
+  if (!dev) {
+    const uint64_t S = mr.n_segs;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_perm, mr.seg_perm, (NK + S) * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_offsets, mr.seg_offsets, (S + 1) * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_coll, mr.seg_coll, S * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_key, mr.seg_key, S * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.seg_active, mr.seg_active, S * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(M.status, mr.status, D * 4, hipMemcpyDeviceToHost));
+  } else if (!c->async) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return c->prof ? collect_prof(c) : 0;
+}
+
 int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int memspace) {
   if (!bt || !res) return fail(c, "null batch/result");
   if (memspace != CW_MEM_HOST) return fail(c, "cw_weft_lists: only CW_MEM_HOST is supported");
@@ -7487,6 +7601,7 @@ static const struct {
     {"map_small", &cw_ctx::map_small, 0, UINT32_MAX},
     {"map_fused", &cw_ctx::map_fused, 0, UINT32_MAX},
     {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
+    {"map_weft_fused", &cw_ctx::map_weft_fused, 0, 1},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
     {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
@@ -7593,6 +7708,12 @@ int cw_weft_lists(cw_ctx *c, const cw_weft_batch *b, cw_weft_result *r, int mems
   if (!c) return -1;
   c->err.clear();
   return weft_lists_impl(c, b, r, memspace);
+}
+
+int cw_weft_maps(cw_ctx *c, const cw_map_weft_batch *b, cw_map_weft_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return weft_maps_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,

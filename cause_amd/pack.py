@@ -210,9 +210,12 @@ class PackedMaps:
     ranks: list              # site rank table per collection
 
 
-def pack_maps(docs) -> PackedMaps:
+def pack_maps(docs, extra_ids=None, min_site_bits: int = 0) -> PackedMaps:
     """Pack a batch of map collections (each an iterable of ``(id, cause, value)``
-    nodes; maps have no root node of their own).  Keys get batch-wide tokens in
+    nodes; maps have no root node of their own).  ``extra_ids[d]``: ids that must
+    be ranked and fit the layout in collection d without being nodes (weft
+    cuts); ``min_site_bits``: the least site field (cw_weft_maps indexes its cut
+    table by site rank: >= 1).  Keys get batch-wide tokens in
     first-appearance order.  The virtual root [[0 "0" 0] nil nil] packs to 0 and
     so does a cause naming it; every other id packs by its site's rank in
     String.compareTo order, which may put site-ids such as " a " before "0"
@@ -221,7 +224,9 @@ def pack_maps(docs) -> PackedMaps:
     is refused (it would pack onto the root id)."""
     docs = [list(d) for d in docs]
     lay = layout_for([[(n[0], n[1] if valid_id(n[1]) else None, n[2]) for n in d]
-                      + [((0, "0", 0), None, None)] for d in docs])
+                      + [((0, "0", 0), None, None)] for d in docs], extra_ids)
+    if lay.site_bits < min_site_bits:
+        lay = KeyLayout(lay.ts_bits, min_site_bits, lay.tx_bits)
     tok = {}
     off = np.zeros(len(docs) + 1, np.uint64)
     N = sum(len(d) for d in docs)
@@ -231,6 +236,7 @@ def pack_maps(docs) -> PackedMaps:
     j = 0
     for d, nodes in enumerate(docs):
         ids = [n[0] for n in nodes] + [n[1] for n in nodes if valid_id(n[1])] + [ROOT_ID]
+        ids += list(extra_ids[d]) if extra_ids else []
         rank = intern_sites(ids)
         ranks.append(rank)
         pk = lambda i: 0 if i == ROOT_ID else lay.pack(i[0], rank[i[1]], i[2])

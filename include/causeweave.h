@@ -116,6 +116,11 @@ int cw_ctx_set_stream(cw_ctx *ctx, void *hip_stream);
  *    follows -- and then for whatever cw_weave_lists itself waits for; when the
  *    two layouts differ from the previous call's it also uploads them with
  *    blocking copies.  The general union waits for its counts as well.
+ *  - cw_weft_maps (device memory) waits once for the kept offsets -- they are
+ *    the coll_offsets of the weave that follows -- and then for whatever
+ *    cw_weave_maps itself waits for; when the layout or site_bits differ from
+ *    the previous call's it also uploads the layout with blocking copies.  The
+ *    general select waits for its counts instead.
  * A caller that wants to overlap host work with the weave should run it on
  * its own thread or queue the weave behind no other work. */
 int cw_ctx_set_async(cw_ctx *ctx, int async);
@@ -414,6 +419,67 @@ typedef struct {
 
 /* Host memory only (memspace must be CW_MEM_HOST in this version). */
 int cw_weft_lists(cw_ctx *ctx, const cw_weft_batch *batch, cw_weft_result *result, int memspace);
+
+/* Maps: CausalMap's weft (map.cljc:246-247), the same s/weft with the map
+ * weave.  Per collection, ids-to-cut-yarns with the root id filtered out names
+ * at most one cut id per site (the last id given for a site wins):
+ * cut[(d << site_bits) | site_rank] is the packed cut id of that site, 0 = the
+ * site is not named.  The site rank of a node is (id_key >> site_shift) &
+ * (2^site_bits - 1).
+ *   - A named site whose cut id is a node keeps the yarn's ids <= the cut.
+ *   - A named site whose cut id is no node keeps its whole yarn (take-while
+ *     never stops) plus the one-element node [id] from (new-node [id nil]).
+ *     map.cljc:30 destructures it to cause nil, value nil: it is woven as
+ *     [id root-id nil] into the nil key weave -- id = the cut word, cause 0,
+ *     cause_is_id = 2, kind normal, kept_src = UINT32_MAX (the list weft gives
+ *     its [id] node the id itself as value; the map weft gives it nil).
+ *   - Nothing is kept from a site that is not named.  A map has no root node.
+ * The kept nodes come out per collection in input order, then its [id] nodes
+ * by site rank, and are rewoven as cw_weave_maps weaves them (c.map/weave
+ * 1-arity).  Cuts that break causality leave id causes that name no kept node,
+ * or name a kept [id] node: cw_weave_maps gives those the reference's keys and
+ * fold (the nil key, id keys: SURVEY F8c).
+ * status[d] is cw_weave_maps' bits for the kept collection, OR'ed with
+ * CW_STATUS_WEFT when the collection got at least one [id] node.  No
+ * CW_STATUS_ORPHAN is added for an id cause that was cut away: the reference
+ * does not detect it either (a TODO there, shared.cljc:275).  A collection
+ * whose kept set is empty -- no site named, among others -- has status 0 and
+ * no key weaves.
+ * A cut word whose site field is not its own rank is a caller error: the
+ * result for that collection is unspecified but well-formed, and nothing is
+ * read or written outside the collection's cut row and the outputs' bounds.
+ * ::lamport-ts of the result is the caller's to take: the largest cut ts.
+ * Limits: N + (n_colls << site_bits) < 2^32 - 1; per kept collection
+ * cw_weave_maps' limits.  The [id] nodes are ids of the kept batch: a nonzero
+ * nodes.key_bits must cover the cut ids as well.
+ * When every collection has <= 2048 nodes the select stage is one kernel per
+ * pack of collections (mapweft.hip); one larger collection sends the whole call
+ * through the general select (a workgroup per collection, two passes around a
+ * host scan).  Both give the same arrays. */
+typedef struct {
+  cw_map_batch nodes;      /* as cw_weave_maps (coll_offsets: host memory)            */
+  uint32_t site_shift;     /* site rank = (id_key >> site_shift) & (2^site_bits - 1)  */
+  uint32_t site_bits;      /* 1..10                                                   */
+  const uint64_t *cut;     /* [n_colls << site_bits], in `memspace`                   */
+} cw_map_weft_batch;
+
+typedef struct {
+  uint64_t *kept_offsets;  /* HOST [n_colls+1]                                        */
+  uint32_t *kept_src;      /* [N + (n_colls << site_bits)]: collection-local input index
+                              of each kept node, in input order, then UINT32_MAX per
+                              [id] node, by site rank                                 */
+  cw_map_result maps;      /* cw_weave_maps' result for the kept collections; every
+                              index is collection-local into kept_src; seg_perm sized
+                              N + (n_colls << site_bits) + cap_segs                   */
+} cw_map_weft_result;
+
+/* memspace: where the node arrays, cut, kept_src and the arrays of `maps` live
+ * (cut too, unlike cw_weft_lists: at 10^6 collections the table is as large as
+ * an input column, and a device call uploads nothing); coll_offsets and
+ * kept_offsets are always host memory.  In device memory kept_src and the map
+ * result are written in place. */
+int cw_weft_maps(cw_ctx *ctx, const cw_map_weft_batch *batch, cw_map_weft_result *result,
+                 int memspace);
 
 /* ------------------------------------ the distributed giant list (config 5) ---- */
 /* Building blocks for one list spread over several GPUs (cause_amd/giant.py:
