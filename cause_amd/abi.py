@@ -230,6 +230,10 @@ def lib():
         L.cw_weft_lists.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch), C.POINTER(CwWeftResult),
                                     C.c_int]
         L.cw_weft_lists.restype = C.c_int
+        if hasattr(L, "cw_weft_lists_dev"):  # (a build from before it, named by CW_LIB for an A/B run)
+            L.cw_weft_lists_dev.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch),
+                                            C.POINTER(CwWeftResult)]
+            L.cw_weft_lists_dev.restype = C.c_int
         if hasattr(L, "cw_weft_maps"):  # (a build from before it, named by CW_LIB for an A/B run)
             L.cw_weft_maps.argtypes = [C.c_void_p, C.POINTER(CwMapWeftBatch),
                                        C.POINTER(CwMapWeftResult), C.c_int]
@@ -680,6 +684,24 @@ class Weaver:
         w = ListResult(w.weave_perm[:M], w.visible_bits[:(M + 31) // 32], w.visible_count[:D],
                        w.max_ts[:D], w.status[:D], None if w.yarn_perm is None else w.yarn_perm[:M])
         return MergeResult(ko, src[:M], w)
+
+    def weft_lists_device(self, offsets, ptrs, layout, cut_ptr, src_ptr, out_ptrs):
+        """Device-memory call (cw_weft_lists_dev).  ptrs = (id_key, cause_key,
+        kind) device pointers; cut_ptr: uint64[D << site_bits] in device memory;
+        src_ptr: kept_src (uint32); out_ptrs as weave_lists_device; src and
+        every per-node array sized for N + (D << site_bits).  Returns the kept
+        offsets (uint64[D+1])."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        b, off = self._batch(offsets, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2]), layout)
+        wb = CwWeftBatch(b, C.cast(vp(cut_ptr), C.POINTER(C.c_uint64)))
+        ko = np.zeros(len(off), np.uint64)
+        g = lambda n: vp(out_ptrs.get(n))
+        r = CwWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
+                         CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"),
+                                      g("max_ts"), g("status"), g("yarn_perm")))
+        self._check(self._L.cw_weft_lists_dev(self._h, C.byref(wb), C.byref(r)),
+                    "cw_weft_lists_dev")
+        return ko
 
     def weave_maps_device(self, offsets, ptrs, token_bits, key_bits, out_ptrs, cap_segs) -> int:
         """Device-memory call of cw_weave_maps: ptrs = (id_key, cause, cause_is_id,

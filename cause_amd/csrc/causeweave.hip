@@ -4511,6 +4511,13 @@ struct cw_ctx {
     bool fits = false;             // every document has na + nb <= LU_MAXDOC
     LookBack lb;                   // k_list_union's look-back words
   } lmerge;
+  uint32_t list_weft_fused = 1;    // list_weft_fused: one-kernel select stage of the list weft
+  struct ListWeft {                // the layout of the last list weft call, as uploaded
+    std::vector<uint64_t> off;
+    const void *doff = nullptr;    // ... to this buffer
+    bool fits = false;             // every document has <= LW_MAXDOC nodes
+    LookBack lb;                   // k_list_weft's look-back words
+  } lweft;
 };
 
 namespace {
@@ -6124,6 +6131,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "mapmerge.hip"
 #include "mapweft.hip"
 #include "listmerge.hip"
+#include "listweft.hip"
 #include "dist.hip"
 
 namespace {
@@ -7436,75 +7444,79 @@ int weft_maps_impl(cw_ctx *c, const cw_map_weft_batch *bt, cw_map_weft_result *r
   return c->prof ? collect_prof(c) : 0;
 }
 
+// cw_weft_lists / cw_weft_lists_dev: uploads (host memspace), the select stage
+// (listweft.hip), one device-to-host copy of the kept offsets,
+// weave_lists_device and the exact path on the kept arrays, the WEFT bits,
+// copies out (host memspace).
 int weft_lists_impl(cw_ctx *c, const cw_weft_batch *bt, cw_weft_result *res, int memspace) {
   if (!bt || !res) return fail(c, "null batch/result");
-  if (memspace != CW_MEM_HOST) return fail(c, "cw_weft_lists: only CW_MEM_HOST is supported");
+  const bool dev = memspace == CW_MEM_DEVICE;
   const cw_list_batch &L = bt->nodes;
   const uint64_t D = L.n_docs;
   const uint64_t *off = L.doc_offsets;
   // (no per-document limit beyond the batch's)
-  if (check_doc_offsets(c, off, D, 0, 0)) return -1;
+  uint64_t largest;
+  if (check_doc_offsets(c, off, D, 0, 0, &largest)) return -1;
   if (L.site_bits == 0 || L.site_bits > 10) return fail(c, "weft needs site_bits in 1..10");
   if (!bt->cut) return fail(c, "cut is required");
-  const uint64_t N = off[D];
+  const uint64_t N = off[D], NS = D << L.site_bits;
+  // kept nodes: at most the document's nodes plus one [id] node per named site
+  if (N + NS >= 0xFFFFFFFFull) return fail(c, "batch too large");
   cw_list_result &W = res->weave;
   if (!res->kept_offsets || !res->kept_src || !W.weave_perm || !W.visible_count || !W.status)
     return fail(c, "kept_offsets, kept_src, weave_perm, visible_count and status are required");
-  const std::vector<uint32_t> h_off(off, off + D + 1);
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t Ns = std::max<uint64_t>(N, 1), NC = (size_t)D << L.site_bits;
   if (N && (!L.id_key || !L.cause_key || !L.kind)) return fail(c, "null input arrays");
-  uint32_t *koff = scratch_t<uint32_t>(c, "w_koff", D + 1);
-  uint32_t *kcnt = scratch_t<uint32_t>(c, "w_kcnt", D + 1), *kst = scratch_t<uint32_t>(c, "w_kst", D + 1);
-  // kept nodes: at most the document's nodes plus one [id] node per named site
-  const size_t NKcap = Ns + NC;
-  if (N + NC >= 0xFFFFFFFFull) return fail(c, "batch too large");
-  uint64_t *kid = scratch_t<uint64_t>(c, "w_kid", NKcap), *kca = scratch_t<uint64_t>(c, "w_kca", NKcap);
-  uint8_t *kkd = scratch_t<uint8_t>(c, "w_kkd", NKcap);
-  uint32_t *ksrc = scratch_t<uint32_t>(c, "w_ksrc", NKcap);
-  if (!koff || !kcnt || !kst || !kid || !kca || !kkd || !ksrc)
-    return fail(c, "out of device memory (weft)");
+  HIPCHK(c, hipSetDevice(c->device));
   if (!grid_ok(D, 1024)) return fail(c, "batch too large for one dispatch");
-  const uint64_t *id, *ca, *cut;
-  const uint8_t *kd;
-  const uint32_t *doff;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (upload(c, "w_id", L.id_key, N * 8, &id) || upload(c, "w_ca", L.cause_key, N * 8, &ca) ||
-      upload(c, "w_kd", L.kind, N, &kd) || upload(c, "w_cut", bt->cut, NC * 8, &cut) ||
-      upload(c, "w_off", h_off.data(), (D + 1) * 4, &doff))
-    return -1;
   uint64_t *ko = res->kept_offsets;
   ko[0] = 0;
   if (D == 0) return 0;
-  hipLaunchKernelGGL((k_weft_select<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, id, ca, kd,
-                     doff, cut, L.site_shift, L.site_bits, 0, kcnt, koff, kid, kca, kkd, ksrc, kst);
-  if (check_launch(c, "weft_count")) return -1;
-  std::vector<uint32_t> h_cnt(D), h_ko(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), kcnt, D * 4, hipMemcpyDeviceToHost));
-  for (uint64_t d = 0; d < D; d++) {
-    ko[d + 1] = ko[d] + h_cnt[d];
-    h_ko[d] = (uint32_t)ko[d];
+  LwHost h{};
+  h.D = D;
+  h.N = N;
+  h.in = LwIn{L.id_key, L.cause_key, L.kind, nullptr, bt->cut, L.site_shift, L.site_bits};
+  if (!dev) {  // uploads (the cut table every call: it is never cached)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (upload(c, "w_id", L.id_key, N * 8, &h.in.id) || upload(c, "w_ca", L.cause_key, N * 8, &h.in.cause) ||
+        upload(c, "w_kd", L.kind, N, &h.in.kind) || upload(c, "w_cut", bt->cut, NS * 8, &h.in.cut))
+      return -1;
   }
-  h_ko[D] = (uint32_t)ko[D];
-  HIPCHK(c, hipMemcpy(koff, h_ko.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL((k_weft_select<1024>), dim3((uint32_t)D), dim3(1024), 0, c->stream, id, ca, kd,
-                     doff, cut, L.site_shift, L.site_bits, 1, kcnt, koff, kid, kca, kkd, ksrc, kst);
-  if (check_launch(c, "weft_write")) return -1;
+  if (list_weft_layout(c, off, D, largest, &h.in.off)) return -1;
+  // the kept documents (device) and the WEFT words
+  const size_t NKcap = std::max<uint64_t>(N, 1) + NS;
+  uint64_t *kid = scratch_t<uint64_t>(c, "w_kid", NKcap), *kca = scratch_t<uint64_t>(c, "w_kca", NKcap);
+  uint8_t *kkd = scratch_t<uint8_t>(c, "w_kkd", NKcap);
+  uint32_t *ksrc = dev ? res->kept_src : scratch_t<uint32_t>(c, "w_ksrc", NKcap);
+  uint32_t *kst = scratch_t<uint32_t>(c, "w_kst", D + 1);
+  if (!kid || !kca || !kkd || !ksrc || !kst) return fail(c, "out of device memory (weft)");
+  h.out = LwOut{kid, kca, kkd, ksrc, nullptr, kst};
+  {
+    int rc = 1;
+    if (c->list_weft_fused) rc = list_weft_fused(c, h, ko);
+    if (rc == 1) rc = list_weft_general(c, h, ko);  // one oversize document: the whole call
+    if (rc) return -1;
+  }
+  // the kept documents through the list pipeline, in device memory
   const uint64_t NK = ko[D];
   if (ensure_tables(c, D, ko)) return -1;
   cw_list_batch lb = L;
   lb.doc_offsets = ko;
-  cw_list_result lr;
-  if (stage_list_result(c, W, NK, D, &lr)) return -1;
+  cw_list_result lr = W;
+  if (!dev && stage_list_result(c, W, NK, D, &lr)) return -1;
   if (weave_lists_device(c, &lb, kid, kca, kkd, &lr)) return -1;
   if (exact_fixup(c, &lb, kid, kca, kkd, &lr, c->x_hint)) return -1;
+  // the documents that got an [id] node: WEFT joins the weave's bits
   hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, kst,
                      lr.status, (uint32_t)D);
   if (check_launch(c, "or_status")) return -1;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (NK) HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
-  if (unstage_list_result(c, lr, NK, D, W) || root_empty_docs(c, ko, D, W.status, false)) return -1;
+  if (dev) {
+    if (root_empty_docs(c, ko, D, lr.status, true)) return -1;
+    if (!c->async) HIPCHK(c, hipStreamSynchronize(c->stream));
+  } else {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (NK) HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
+    if (unstage_list_result(c, lr, NK, D, W) || root_empty_docs(c, ko, D, W.status, false)) return -1;
+  }
   return c->prof ? collect_prof(c) : 0;
 }
 
@@ -7603,6 +7615,7 @@ static const struct {
     {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
     {"map_weft_fused", &cw_ctx::map_weft_fused, 0, 1},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
+    {"list_weft_fused", &cw_ctx::list_weft_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
     {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
 };
@@ -7707,7 +7720,14 @@ int cw_merge_maps(cw_ctx *c, const cw_map_merge_batch *b, cw_map_merge_result *r
 int cw_weft_lists(cw_ctx *c, const cw_weft_batch *b, cw_weft_result *r, int memspace) {
   if (!c) return -1;
   c->err.clear();
-  return weft_lists_impl(c, b, r, memspace);
+  if (memspace != CW_MEM_HOST) return fail(c, "cw_weft_lists: only CW_MEM_HOST is supported");
+  return weft_lists_impl(c, b, r, CW_MEM_HOST);
+}
+
+int cw_weft_lists_dev(cw_ctx *c, const cw_weft_batch *b, cw_weft_result *r) {
+  if (!c) return -1;
+  c->err.clear();
+  return weft_lists_impl(c, b, r, CW_MEM_DEVICE);
 }
 
 int cw_weft_maps(cw_ctx *c, const cw_map_weft_batch *b, cw_map_weft_result *r, int memspace) {

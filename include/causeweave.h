@@ -121,6 +121,11 @@ int cw_ctx_set_stream(cw_ctx *ctx, void *hip_stream);
  *    cw_weave_maps itself waits for; when the layout or site_bits differ from
  *    the previous call's it also uploads the layout with blocking copies.  The
  *    general select waits for its counts instead.
+ *  - cw_weft_lists_dev waits once for the kept offsets -- they are the
+ *    doc_offsets of the weave that follows -- and then for whatever
+ *    cw_weave_lists itself waits for; when the layout differs from the
+ *    previous call's it also uploads it with blocking copies.  The general
+ *    select waits for its counts instead.
  * A caller that wants to overlap host work with the weave should run it on
  * its own thread or queue the weave behind no other work. */
 int cw_ctx_set_async(cw_ctx *ctx, int async);
@@ -405,7 +410,8 @@ int cw_merge_maps(cw_ctx *ctx, const cw_map_merge_batch *batch, cw_map_merge_res
  * N + (n_docs << site_bits) nodes. */
 typedef struct {
   cw_list_batch nodes;   /* site_bits must be 1..10                           */
-  const uint64_t *cut;   /* HOST memory [n_docs << site_bits]                */
+  const uint64_t *cut;   /* [n_docs << site_bits]: HOST memory for
+                            cw_weft_lists, DEVICE memory for cw_weft_lists_dev */
 } cw_weft_batch;
 
 typedef struct {
@@ -417,8 +423,26 @@ typedef struct {
                              into kept_src                                     */
 } cw_weft_result;
 
-/* Host memory only (memspace must be CW_MEM_HOST in this version). */
+/* Host memory only (memspace must be CW_MEM_HOST; the device call is
+ * cw_weft_lists_dev). */
 int cw_weft_lists(cw_ctx *ctx, const cw_weft_batch *batch, cw_weft_result *result, int memspace);
+
+/* The same call in device memory: nodes.id_key / cause_key / kind, cut (at 10^4
+ * documents x 2^10 ranks the table is as large as an input column, and a device
+ * call uploads nothing), kept_src and every array of `weave` are device
+ * memory; nodes.doc_offsets and kept_offsets are host memory.  kept_src and
+ * the weave arrays (room for N + (n_docs << site_bits) nodes) are written in
+ * place, the CW_STATUS_ROOT bit of a document whose kept set is empty included.
+ * visible_bits, max_ts and yarn_perm may be NULL as in cw_weave_lists.
+ * When every document has <= 65,535 nodes the select stage is one kernel, a
+ * workgroup per document (listweft.hip); one larger document sends the whole
+ * call through the general select (two passes around a host scan).  Both give
+ * the same arrays, and cw_weft_lists takes the same routes after its uploads.
+ * Errors (< 0, cw_last_error, nothing written): null batch / result / cut,
+ * site_bits outside 1..10, doc_offsets that do not start at 0 or decrease,
+ * N + (n_docs << site_bits) >= 2^32 - 1, a null required output, null inputs
+ * with N > 0. */
+int cw_weft_lists_dev(cw_ctx *ctx, const cw_weft_batch *batch, cw_weft_result *result);
 
 /* Maps: CausalMap's weft (map.cljc:246-247), the same s/weft with the map
  * weave.  Per collection, ids-to-cut-yarns with the root id filtered out names
