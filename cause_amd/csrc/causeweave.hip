@@ -2028,7 +2028,6 @@ __device__ __forceinline__ void tree_l_doc(
   __syncthreads();
   stamp(0);
   auto special_at = [&](uint32_t r) -> bool { return (spec_bm[r >> 5] >> (r & 31)) & 1u; };
-  auto hide_at = [&](uint32_t r) -> bool { return (hide_bm[r >> 5] >> (r & 31)) & 1u; };
   uint32_t qpar[IT];
   auto load_par = [&](uint32_t r0) {
 #pragma unroll
@@ -2247,103 +2246,109 @@ __device__ __forceinline__ void tree_l_doc(
   __syncthreads();
   // sweep 2: preorder successors; thr(r) = ns(r) ?: thr(e(r)) with the earlier
   // tiles' threads in tab (u16) and this tile's resolved by pointer jumping.
-  // Tile loads run two tiles ahead.
+  // Of the tile buffer it needs T and the tile's splitters alone, so its tiles
+  // are TILE2 ranks, not sweep 1's TILE_T.  Tile loads run one tile ahead.
   constexpr uint32_t RES = 0x80000000u;
-  uint32_t *const T = hbuf;
+  constexpr uint32_t TILE2 = 2 * TILE_T, IT2 = TILE2 / NT;
+  static_assert(TILE2 % TILE_T == 0 && TILE2 * 4 <= 4 * TILE_T * 4, "sweep 2's T fits hbuf");
+  static_assert(2 * TILE2 * 4 <= 4 * TILE_T * 4, "T and the tile's splitters fit hbuf");
+  uint32_t *const T = hbuf, *const SP = hbuf + TILE2;
   struct Q {
-    uint32_t fs[IT], ns[IT];
+    uint32_t fs[IT2], ns[IT2];
   };
   auto load_tile = [&](Q &q, uint32_t r0) {
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
+    for (uint32_t k = 0; k < IT2; k++) {
       const uint32_t r = r0 + k * NT + tid;
       const bool ok = r < n;
       q.fs[k] = ok ? lane_at(fcSD, r) : 0u;
       q.ns[k] = ok ? lane_at(nscD, r) : 0u;
     }
   };
-  // one tile: X holds its loads (and is refilled with tile r0 + 2 TILE_T)
+  // one tile: X holds its loads (and is refilled with tile r0 + TILE2)
   auto tile2f = [&](uint32_t r0, Q &X, auto fullc) {
     constexpr bool F = decltype(fullc)::value;
-    const uint32_t len = F ? TILE_T : min((uint32_t)TILE_T, n - r0);
-    uint32_t flg[IT], fcr[IT];
+    const uint32_t len = F ? TILE2 : min((uint32_t)TILE2, n - r0);
+    uint32_t flg[IT2], fcr[IT2], tv[IT2];
+    // the splitters of the tile's blocks: one hash a block, not one a rank
+    const uint32_t b0 = r0 >> log2k, nb = ((r0 + len - 1) >> log2k) - b0 + 1;
+    for (uint32_t b = tid; b < nb; b += NT) SP[b] = split_node(d, b0 + b, log2k, n);
+    // every table read of the tile's items first, whether the item needs it or
+    // not (one it does not need reads entry 0): no read depends on another, so
+    // their LDS latencies overlap instead of adding up branch by branch
+    uint32_t tr[IT2], te[IT2], sw[IT2], hw[IT2];
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
+    for (uint32_t k = 0; k < IT2; k++) {
+      const uint32_t j = k * NT + tid, r = F || j < len ? r0 + j : 0u;
+      const uint32_t ns = X.ns[k], e = ns & NSC_UP ? ns & ~NSC_UP : 0u;
+      tr[k] = tab[r];
+      te[k] = tab[e < r0 ? e : 0u];
+      sw[k] = spec_bm[r >> 5];
+      hw[k] = hide_bm[X.fs[k] >> 5];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < IT2; k++) {
       const uint32_t j = k * NT + tid, r = r0 + j;
       flg[k] = 0;
       fcr[k] = 0;
+      tv[k] = RES;
       if (j >= len) continue;
-      fcr[k] = X.fs[k] ? X.fs[k] : (uint32_t)tab[r];
-      const bool sp = special_at(r);
-      uint32_t tv;
-      if (r == 0) {
-        tv = RES | SUCC_END;
-      } else {
-        uint32_t ns = X.ns[k], e = 0;
-        if (ns & NSC_UP) {
-          e = ns & ~NSC_UP;
-          ns = 0;
-        }
-        if (ns) {
-          tv = RES | ns;
-        } else if (e >= r0) {
-          tv = e - r0;
-        } else {
-          const uint32_t t = tab[e];
-          tv = RES | (t == TL_END ? SUCC_END : t);
-        }
-      }
-      T[j] = tv;
       const uint32_t fs = X.fs[k];
-      const bool vis = !sp && r != 0 && !(fs && hide_at(fs));
-      const bool split = r == split_node(d, r >> log2k, log2k, n);
-      flg[k] = (vis ? LINK_VIS : 0u) | (split ? LINK_SPLIT : 0u);
+      fcr[k] = fs ? fs : tr[k];
+      const bool sp = (sw[k] >> (r & 31)) & 1u;
+      uint32_t ns = X.ns[k], e = 0;
+      if (ns & NSC_UP) {
+        e = ns & ~NSC_UP;
+        ns = 0;
+      }
+      uint32_t t = RES | (te[k] == TL_END ? SUCC_END : te[k]);
+      if (e >= r0) t = e - r0;
+      if (ns) t = RES | ns;
+      if (r == 0) t = RES | SUCC_END;
+      T[j] = tv[k] = t;
+      const bool vis = !sp && r != 0 && !(fs && ((hw[k] >> (fs & 31)) & 1u));
+      flg[k] = vis ? LINK_VIS : 0u;
     }
-    if (r0 + 2 * TILE_T < n) load_tile(X, r0 + 2 * TILE_T);
+    if (r0 + TILE2 < n) load_tile(X, r0 + TILE2);
     __syncthreads();
     stamp(5);
     // pointer jumping without barriers: every value in T is an ancestor's
     // pointer or a resolved thread at any time, so a lane may read its
     // target's entry whenever it likes; each lane stops when its own entries
-    // are resolved (targets are smaller indices of the same tile)
+    // are resolved (targets are smaller indices of the same tile).  Only its
+    // owner writes an entry, so the owner follows it in a register.
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
-      const uint32_t j = k * NT + tid;
-      if (j < len) {
-        uint32_t t = T[j];
-        while (!(t & RES)) {
-          t = T[t];
-          T[j] = t;
-        }
+    for (uint32_t k = 0; k < IT2; k++) {
+      uint32_t t = tv[k];
+      while (!(t & RES)) {
+        t = T[t];
+        T[k * NT + tid] = t;
       }
+      tv[k] = t;
     }
     // (no barrier here: a lane writes out only the entries it resolved itself,
     // into tab and the links, which no jumping lane reads; the barrier after
-    // the writes keeps the next tile's T and its reads of tab apart -- round 6)
+    // the writes keeps the next tile's T, its splitters and its reads of tab
+    // apart -- round 6)
     stamp(6);
 #pragma unroll
-    for (uint32_t k = 0; k < IT; k++) {
+    for (uint32_t k = 0; k < IT2; k++) {
       const uint32_t j = k * NT + tid, r = r0 + j;
       if (j >= len) continue;
-      const uint32_t th = T[j] & ~RES;
+      const uint32_t th = tv[k] & ~RES;
       tab[r] = (uint16_t)(th == SUCC_END ? TL_END : th);
+      if (SP[(r >> log2k) - b0] == r) flg[k] |= LINK_SPLIT;
       lane_at(linkD, r) = (fcr[k] ? fcr[k] : th) | flg[k];
     }
     __syncthreads();
     stamp(7);
   };
-  auto tile2 = [&](uint32_t r0, Q &X) {
-    if (r0 + TILE_T <= n) tile2f(r0, X, std::true_type());
-    else tile2f(r0, X, std::false_type());
-  };
-  Q qa, qb;
-  load_tile(qa, 0);
-  if (TILE_T < n) load_tile(qb, TILE_T);
+  Q q;
+  load_tile(q, 0);
   stamp(4);
-  for (uint32_t r0 = 0; r0 < n; r0 += 2 * TILE_T) {
-    tile2(r0, qa);
-    if (r0 + TILE_T < n) tile2(r0 + TILE_T, qb);
-  }
+  uint32_t r0s = 0;
+  for (; r0s + TILE2 <= n; r0s += TILE2) tile2f(r0s, q, std::true_type());
+  if (r0s < n) tile2f(r0s, q, std::false_type());
   if (PROF && tid == 0)
     for (int ph = 0; ph < 16; ph++) tprof[(size_t)d * 16 + ph] = tacc[ph];
 }
