@@ -119,6 +119,29 @@ class CwMapWeftResult(C.Structure):
                 ("maps", CwMapResult)]
 
 
+class CwRenderBatch(C.Structure):
+    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", C.POINTER(C.c_uint64)),
+                ("weave_perm", C.c_void_p), ("visible_bits", C.c_void_p), ("perm16", C.c_uint32),
+                ("value_size", C.c_uint32), ("value", C.c_void_p)]
+
+
+class CwRenderResult(C.Structure):
+    _fields_ = [("rendered_offsets", C.POINTER(C.c_uint64)), ("rendered_src", C.c_void_p),
+                ("rendered_value", C.c_void_p)]
+
+
+class CwMapRenderBatch(C.Structure):
+    _fields_ = [("n_colls", C.c_uint64), ("n_segs", C.c_uint64), ("seg_coll", C.c_void_p),
+                ("seg_key", C.c_void_p), ("seg_active", C.c_void_p),
+                ("coll_offsets", C.POINTER(C.c_uint64)), ("value_size", C.c_uint32),
+                ("value", C.c_void_p)]
+
+
+class CwMapRenderResult(C.Structure):
+    _fields_ = [("entry_offsets", C.POINTER(C.c_uint64)), ("entry_key", C.c_void_p),
+                ("entry_src", C.c_void_p), ("entry_value", C.c_void_p)]
+
+
 class CwRankedList(C.Structure):
     _fields_ = [("n", C.c_uint64), ("par", C.c_void_p), ("kind", C.c_void_p), ("val", C.c_void_p)]
 
@@ -238,6 +261,12 @@ def lib():
             L.cw_weft_maps.argtypes = [C.c_void_p, C.POINTER(CwMapWeftBatch),
                                        C.POINTER(CwMapWeftResult), C.c_int]
             L.cw_weft_maps.restype = C.c_int
+        L.cw_render_lists.argtypes = [C.c_void_p, C.POINTER(CwRenderBatch),
+                                      C.POINTER(CwRenderResult), C.c_int]
+        L.cw_render_lists.restype = C.c_int
+        L.cw_render_maps.argtypes = [C.c_void_p, C.POINTER(CwMapRenderBatch),
+                                     C.POINTER(CwMapRenderResult), C.c_int]
+        L.cw_render_maps.restype = C.c_int
         P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
         L.cw_sort_keys.argtypes = [P, P, U64, U32, P, P]
         L.cw_lookup_keys.argtypes = [P, P, U64, P, U64, U32, P, P]
@@ -321,6 +350,36 @@ class MapWeftResult:
     offsets: np.ndarray      # uint64[D+1] kept collections
     src: np.ndarray          # uint32[M] kept nodes in input order, then UINT32_MAX per [id] node
     maps: MapResult          # every index is collection-local into src
+
+
+@dataclass
+class RenderResult:
+    """Rendered nodes per document (cw_render_lists)."""
+    offsets: np.ndarray        # uint64[D+1] rendered documents; their differences are `count`
+    src: np.ndarray            # uint32[R] doc-local index of each rendered node, weave order
+    value: np.ndarray | None   # [R] its value word (the dtype of the value column)
+
+
+@dataclass
+class MapRenderResult:
+    """Non-blank key weaves per collection (cw_render_maps)."""
+    offsets: np.ndarray        # uint64[D+1]; their differences are `count-`
+    key: np.ndarray            # uint64[R] seg_key of each entry, ascending in a collection
+    src: np.ndarray            # uint32[R] collection-local index of its active node
+    value: np.ndarray | None   # [R] the active node's value word
+
+
+_VALUE_DTYPES = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}
+
+
+def _value_column(value):
+    """A value column as an unsigned array of its item size (1, 2, 4 or 8 bytes)."""
+    if value is None:
+        return None
+    v = np.ascontiguousarray(value)
+    if v.dtype.itemsize not in _VALUE_DTYPES:
+        raise ValueError("value words of 1, 2, 4 or 8 bytes")
+    return v.view(_VALUE_DTYPES[v.dtype.itemsize])
 
 
 def _ptr(a):
@@ -878,3 +937,95 @@ class Weaver:
         return MapWeftResult(ko, src[:M], MapResult(
             out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
             out.seg_perm[:M + S], out.status[:D]))
+
+    # --- render: causal->edn / count of woven lists and maps -----------------------
+    def render_lists_device(self, offsets, perm_ptr, bits_ptr, src_ptr=None, value_ptr=None,
+                            value_size=0, out_value_ptr=None, perm16=False) -> np.ndarray:
+        """Device-memory call of cw_render_lists: raw device pointers to
+        weave_perm (uint32, or uint16 with perm16), visible_bits, the value
+        column and the outputs rendered_src / rendered_value (None = NULL).
+        Returns the rendered offsets (uint64[D+1])."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        vp = lambda p: C.c_void_p(p) if p else None
+        b = CwRenderBatch(len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_uint64)), vp(perm_ptr),
+                          vp(bits_ptr), int(perm16), value_size, vp(value_ptr))
+        ro = np.zeros(len(off), np.uint64)
+        r = CwRenderResult(ro.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr), vp(out_value_ptr))
+        self._check(self._L.cw_render_lists(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
+                    "cw_render_lists")
+        return ro
+
+    def render_lists(self, offsets, weave_perm, visible_bits, value=None) -> RenderResult:
+        """Host-memory call of cw_render_lists: the rendered nodes of every
+        document from a weave's weave_perm (uint32, or uint16: perm16) and
+        visible_bits; value: one word of 1, 2, 4 or 8 bytes per node."""
+        off = np.ascontiguousarray(offsets, np.uint64)
+        perm = np.ascontiguousarray(weave_perm)
+        if perm.dtype != np.uint16:
+            perm = np.ascontiguousarray(perm, np.uint32)
+        bits = np.ascontiguousarray(visible_bits, np.uint32)
+        N = len(perm)
+        val = _value_column(value)
+        if int(off[-1]) != N or len(bits) < (N + 31) // 32 or (val is not None and len(val) != N):
+            raise ValueError("offsets[-1] / weave_perm / visible_bits / value sizes differ")
+        ro = np.zeros(len(off), np.uint64)
+        src = np.zeros(max(N, 1), np.uint32)
+        oval = None if val is None else np.zeros(max(N, 1), val.dtype)
+        b = CwRenderBatch(len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(perm),
+                          _ptr(bits), int(perm.dtype == np.uint16),
+                          0 if val is None else val.dtype.itemsize, _ptr(val))
+        r = CwRenderResult(ro.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src), _ptr(oval))
+        self._check(self._L.cw_render_lists(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
+                    "cw_render_lists")
+        R = int(ro[-1])
+        return RenderResult(ro, src[:R], None if oval is None else oval[:R])
+
+    def render_maps_device(self, n_colls, n_segs, coll_ptr, key_ptr, active_ptr, key_out_ptr=None,
+                           src_ptr=None, coll_offsets=None, value_ptr=None, value_size=0,
+                           out_value_ptr=None) -> np.ndarray:
+        """Device-memory call of cw_render_maps: raw device pointers to seg_coll,
+        seg_key, seg_active (cw_weave_maps' result), the value column and the
+        outputs entry_key / entry_src / entry_value (None = NULL); coll_offsets
+        (host) only with a value column.  Returns the entry offsets
+        (uint64[n_colls+1])."""
+        vp = lambda p: C.c_void_p(p) if p else None
+        co = None if coll_offsets is None else np.ascontiguousarray(coll_offsets, np.uint64)
+        b = CwMapRenderBatch(n_colls, n_segs, vp(coll_ptr), vp(key_ptr), vp(active_ptr),
+                             None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint64)),
+                             value_size, vp(value_ptr))
+        eo = np.zeros(n_colls + 1, np.uint64)
+        r = CwMapRenderResult(eo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(key_out_ptr), vp(src_ptr),
+                              vp(out_value_ptr))
+        self._check(self._L.cw_render_maps(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
+                    "cw_render_maps")
+        return eo
+
+    def render_maps(self, n_colls, seg_coll, seg_key, seg_active, coll_offsets=None,
+                    value=None) -> MapRenderResult:
+        """Host-memory call of cw_render_maps on the seg_coll / seg_key /
+        seg_active of a MapResult; value (with coll_offsets): one word of 1, 2,
+        4 or 8 bytes per node, collection-local order."""
+        sc = np.ascontiguousarray(seg_coll, np.uint32)
+        sk = np.ascontiguousarray(seg_key, np.uint64)
+        sa = np.ascontiguousarray(seg_active, np.int64)
+        S = len(sc)
+        if len(sk) != S or len(sa) != S:
+            raise ValueError("seg_coll / seg_key / seg_active sizes differ")
+        val = _value_column(value)
+        co = None
+        if val is not None:
+            co = np.ascontiguousarray(coll_offsets, np.uint64)
+            if len(co) != n_colls + 1 or int(co[-1]) != len(val):
+                raise ValueError("coll_offsets / value sizes")
+        eo = np.zeros(n_colls + 1, np.uint64)
+        key, src = np.zeros(max(S, 1), np.uint64), np.zeros(max(S, 1), np.uint32)
+        oval = None if val is None else np.zeros(max(S, 1), val.dtype)
+        b = CwMapRenderBatch(n_colls, S, _ptr(sc), _ptr(sk), _ptr(sa),
+                             None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint64)),
+                             0 if val is None else val.dtype.itemsize, _ptr(val))
+        r = CwMapRenderResult(eo.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(key), _ptr(src),
+                              _ptr(oval))
+        self._check(self._L.cw_render_maps(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
+                    "cw_render_maps")
+        R = int(eo[-1])
+        return MapRenderResult(eo, key[:R], src[:R], None if oval is None else oval[:R])

@@ -365,6 +365,47 @@ def count(ct):
     return len(causal_list_to_list(ct))
 
 
+def lists_to_edn(cts):
+    """causal-list->edn (list.cljc:57-66) of many list cts, woven and rendered
+    on the GPU (cw_weave_lists, then cw_render_lists): per ct the list
+    causal_list_to_edn gives after a reweave, without the host filter.  When
+    every value of the batch is a single character the values go along as a
+    code-point column and the documents come back as rendered_value;
+    otherwise rendered_src is mapped back to the nodes' values."""
+    docs = [[(i, b[0], b[1]) for i, b in ct["nodes"].items()] for ct in cts]
+    w = weaver()
+    try:
+        b = pack.pack_lists(docs)
+        res = w.weave_lists(b.offsets, b.id_key, b.cause_key, b.kind, b.layout, yarns=False)
+    except pack.KeyRangeError:  # ids over 63 bits: the K128 layout
+        b = pack.pack_lists_k128(docs)
+        res = w.weave_lists_k128(b.offsets, b.id_key, b.cause_key, b.kind, yarns=False)
+    for st in res.status.tolist():
+        if st & (abi.STATUS_DUP | abi.STATUS_INTERNAL):
+            raise CauseError(f"document outside the weave's domain (status {st})", {"weave-domain"})
+    # root and special nodes never render (hide?, list.cljc:48-55): their word is 0
+    plain = [n[2] for nodes in docs for n in nodes if n[0] != ROOT_ID and not _special(n[2])]
+    chars = all(isinstance(v, str) and len(v) == 1 for v in plain)
+    codes = None
+    if chars:
+        codes = np.array([ord(n[2]) if isinstance(n[2], str) and len(n[2]) == 1 else 0
+                          for nodes in docs for n in nodes], np.uint32)
+    r = w.render_lists(b.offsets, res.weave_perm, res.visible_bits, codes)
+    out = []
+    for d, nodes in enumerate(docs):
+        lo, hi = int(r.offsets[d]), int(r.offsets[d + 1])
+        if chars:
+            out.append([chr(c) for c in r.value[lo:hi].tolist()])
+        else:
+            out.append([causal_to_edn(nodes[s][2]) for s in r.src[lo:hi].tolist()])
+    return out
+
+
+def _special(v):
+    """shared.cljc:21 special-keywords"""
+    return pack.kind_of(v) != pack.KIND_NORMAL
+
+
 # ------------------------------------------------------------------------- maps
 # map.cljc: the map interface over cw_weave_maps.  A map ct's ``weave`` is
 # {key: key weave (root first)}; ``_active`` is {key: active node or BLANK}.
@@ -417,18 +458,21 @@ def _segs_by_coll(res):
     return segs_of
 
 
+def _seg_key(k, pm, d):
+    """The map key a seg_key word of collection d stands for."""
+    if k == pack.NIL:
+        return None
+    if k >> 63:
+        return _unpack_id(k & ((1 << 63) - 1), pm.layout, pm.ranks[d])
+    return pm.keys[k]
+
+
 def _key_weaves(res, segs, nodes, pm, d):
     """{key: key weave} and {key: active node} of collection d from the key
     weaves `segs` of a cw_map_result, whose indices point into `nodes`."""
     weave, active = {}, {}
     for s in segs:
-        k = int(res.seg_key[s])
-        if k == pack.NIL:
-            key = None
-        elif k >> 63:
-            key = _unpack_id(k & ((1 << 63) - 1), pm.layout, pm.ranks[d])
-        else:
-            key = pm.keys[k]
+        key = _seg_key(int(res.seg_key[s]), pm, d)
         # nodes are woven as [id cause-in-weave v] (map.cljc:35-41)
         weave[key] = [ROOT_NODE] + [
             (nodes[p][0], nodes[p][1] if pack.valid_id(nodes[p][1]) else ROOT_ID, nodes[p][2])
@@ -603,6 +647,28 @@ def causal_map_to_edn(ct):
     """map.cljc:94-103: the active value of every key, nested causal values
     materialised (s/causal->edn, map.cljc:101)."""
     return {n[1]: causal_to_edn(n[2]) for n in ct["_active"].values() if n is not BLANK}
+
+
+def maps_to_edn(cts):
+    """causal-map->edn (map.cljc:94-103) of many map cts, woven and rendered on
+    the GPU (cw_weave_maps, then cw_render_maps): per ct the dict
+    causal_map_to_edn gives after a reweave, its keys in ascending key-token
+    order (the reference's reduce-kv order over a hash map is unspecified)."""
+    docs = [[(i, b[0], b[1]) for i, b in ct["nodes"].items()] for ct in cts]
+    pm = pack.pack_maps(docs)
+    w = weaver()
+    res = w.weave_maps(pm.offsets, pm.id_key, pm.cause, pm.cause_is_id, pm.kind, pm.token_bits,
+                       pm.layout.key_bits)
+    for st in res.status.tolist():
+        if st & (abi.STATUS_DUP | abi.STATUS_MAP_KEY | abi.STATUS_INTERNAL):
+            raise CauseError(f"map outside the weave's domain (status {st})", {"weave-domain"})
+    r = w.render_maps(len(docs), res.seg_coll, res.seg_key, res.seg_active)
+    out = []
+    for d, nodes in enumerate(docs):
+        lo, hi = int(r.offsets[d]), int(r.offsets[d + 1])
+        out.append({_seg_key(k, pm, d): causal_to_edn(nodes[s][2])
+                    for k, s in zip(r.key[lo:hi].tolist(), r.src[lo:hi].tolist())})
+    return out
 
 
 def causal_map_to_list(ct):

@@ -4523,6 +4523,14 @@ struct cw_ctx {
     bool fits = false;             // every document has <= LW_MAXDOC nodes
     LookBack lb;                   // k_list_weft's look-back words
   } lweft;
+  struct Render {                  // cw_render_lists / cw_render_maps (render.hip)
+    struct Layout {                // the offsets of the last call, as uploaded
+      std::vector<uint64_t> off;
+      const void *doff = nullptr;  // ... to this buffer
+      const void *tdoc = nullptr;  // ... and the tiles' first documents to this one
+    } lists, maps;
+    LookBack lb;                   // k_render's look-back words
+  } render;
 };
 
 namespace {
@@ -6137,6 +6145,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "mapweft.hip"
 #include "listmerge.hip"
 #include "listweft.hip"
+#include "render.hip"
 #include "dist.hip"
 
 namespace {
@@ -7739,6 +7748,18 @@ int cw_weft_maps(cw_ctx *c, const cw_map_weft_batch *b, cw_map_weft_result *r, i
   if (!c) return -1;
   c->err.clear();
   return weft_maps_impl(c, b, r, memspace);
+}
+
+int cw_render_lists(cw_ctx *c, const cw_render_batch *b, cw_render_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return render_lists_impl(c, b, r, memspace);
+}
+
+int cw_render_maps(cw_ctx *c, const cw_map_render_batch *b, cw_map_render_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return render_maps_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,

@@ -126,6 +126,12 @@ int cw_ctx_set_stream(cw_ctx *ctx, void *hip_stream);
  *    cw_weave_lists itself waits for; when the layout differs from the
  *    previous call's it also uploads it with blocking copies.  The general
  *    select waits for its counts instead.
+ *  - cw_render_lists / cw_render_maps wait once for the rendered / entry
+ *    offsets, (n_docs + 1) or (n_colls + 1) words of 8 bytes (maps: one word
+ *    more, whether seg_coll was in order), and for nothing else: the offsets
+ *    are host memory, so the call has returned them when it returns.  When the
+ *    offsets differ from the previous call's they are also uploaded with
+ *    blocking copies (cw_render_maps: only with a value column).
  * A caller that wants to overlap host work with the weave should run it on
  * its own thread or queue the weave behind no other work. */
 int cw_ctx_set_async(cw_ctx *ctx, int async);
@@ -504,6 +510,115 @@ typedef struct {
  * result are written in place. */
 int cw_weft_maps(cw_ctx *ctx, const cw_map_weft_batch *batch, cw_map_weft_result *result,
                  int memspace);
+
+/* --------------------------------------------------------------- render ---- */
+/* The user-facing result of a woven batch, compacted on the device:
+ *   causal-list->list (list.cljc:68-72)  -> rendered_src
+ *   causal-list->edn  (list.cljc:57-66)  -> rendered_value (documents of scalars)
+ *   count             (list.cljc:77)     -> rendered_offsets[d + 1] - rendered_offsets[d]
+ * It is the reference's filter and nothing else: position g of the global
+ * weave is emitted iff bit g of visible_bits is set (not hide?, list.cljc:
+ * 48-55), in weave order.  The call takes the result arrays of cw_weave_lists
+ * (and _k32 / _k128), of cw_merge_lists (doc_offsets = merged_offsets) and of
+ * cw_weft_lists / _dev (doc_offsets = kept_offsets) as they stand; it reads no
+ * id, cause or kind column and is a pure function of its inputs.
+ *   rendered_offsets[d] = the number of set bits below position doc_offsets[d],
+ *   rendered_offsets[n_docs] the total R.  Empty documents and documents that
+ *   render nothing are legal: equal consecutive offsets.
+ *   rendered_src[rendered_offsets[d] + k] = weave_perm entry (the doc-local
+ *   index) of the k-th rendered node of document d.
+ *   rendered_value[same] = value[doc_offsets[d] + src].  `value` holds one
+ *   word of value_size bytes per node in the order weave_perm indexes: code
+ *   points (the rendered values of a document are then its string), value
+ *   tokens, ...  A value column in merged or kept order is the caller's to
+ *   build (through merged_src / kept_src).  Nested causal values (refs) stay
+ *   opaque tokens, as everywhere in this ABI: recursion into them is host work
+ *   (s/causal->edn, shared.cljc:320-328).
+ * weave_perm of a CW_STATUS_DUP / INTERNAL document is well-formed but
+ * unspecified, so src is checked against the document's size: an out-of-range
+ * src gets value 0, and no access leaves the caller's arrays whatever
+ * weave_perm holds.  Bits of visible_bits at positions >= N are ignored.
+ * Limits: N = doc_offsets[n_docs] < 2^32 - 1; no limit on a document. */
+typedef struct {
+  uint64_t n_docs;
+  const uint64_t *doc_offsets;  /* HOST [n_docs+1]: the layout the weave arrays were
+                                   written by (doc_offsets, merged_offsets or kept_offsets) */
+  const void *weave_perm;       /* [N] uint32_t, or uint16_t when perm16 = 1; may be NULL
+                                   in the count-only call                                  */
+  const uint32_t *visible_bits; /* [(N+31)/32]                                             */
+  uint32_t perm16;              /* 1: every document < 65,536 nodes (cw_list_batch_k32)    */
+  uint32_t value_size;          /* 0 (no value column), 1, 2, 4 or 8 bytes                 */
+  const void *value;            /* [N] elements of value_size, or NULL                     */
+} cw_render_batch;
+
+typedef struct {
+  uint64_t *rendered_offsets;   /* HOST [n_docs+1]                                         */
+  uint32_t *rendered_src;       /* [N] or NULL                                             */
+  void *rendered_value;         /* [N] elements of value_size, or NULL                     */
+} cw_render_result;
+
+/* memspace: where weave_perm, visible_bits, value, rendered_src and
+ * rendered_value live; the two offsets arrays are always host memory.  In
+ * device memory nothing but the offsets is copied and the outputs are written
+ * in place; a host-memory call stages through the context's scratch.  Either
+ * way exactly R = rendered_offsets[n_docs] elements of rendered_src and
+ * rendered_value are written, nothing past them.
+ * rendered_src and rendered_value may both be NULL: the count-only call.
+ * value and rendered_value go together (with value_size != 0 both or neither;
+ * with value_size = 0 both are ignored).
+ * One kernel, a workgroup per tile of 8,192 weave positions, serves every
+ * document size (render.hip); a second one ranks the document boundaries.
+ * Errors (< 0, cw_last_error, nothing written): null batch / result /
+ * doc_offsets / rendered_offsets; doc_offsets that do not start at 0 or
+ * decrease; N >= 2^32 - 1; value_size outside {0, 1, 2, 4, 8}; exactly one of
+ * value / rendered_value NULL while value_size != 0; perm16 with a document of
+ * >= 65,536 nodes; with N > 0 a null visible_bits, or a null weave_perm while
+ * rendered_src or rendered_value is asked for; a bad memspace. */
+int cw_render_lists(cw_ctx *ctx, const cw_render_batch *batch, cw_render_result *result,
+                    int memspace);
+
+/* Maps: causal-map->list / causal-map->edn (map.cljc:94-109) and count-
+ * (map.cljc:68-73) from cw_weave_maps' result (and cw_merge_maps' / cw_weft_maps'
+ * `maps`): key weave s is emitted iff seg_active[s] >= 0 (not ::blank), in
+ * input order, that is per collection in ascending seg_key order.  (The
+ * reference's reduce-kv runs over a hash map: its order is unspecified, and
+ * this order is one of the orders it may take.)
+ *   entry_offsets[c] = the non-blank key weaves of the collections below c;
+ *   entry_offsets[c + 1] - entry_offsets[c] is count-.  Collections without a
+ *   key weave, or with every key blank, give equal consecutive offsets.
+ *   entry_key / entry_src = seg_key / seg_active (as uint32_t; UINT32_MAX for
+ *   one that does not fit) of each emitted key weave; entry_value = value[coll_offsets[seg_coll] + seg_active], the
+ *   active node's value word, 0 when seg_active is not below the collection's
+ *   size (no access leaves the caller's arrays). */
+typedef struct {
+  uint64_t n_colls, n_segs;      /* n_segs = cw_map_result.n_segs, < 2^32 - 1              */
+  const uint32_t *seg_coll;      /* [n_segs], ascending, as cw_weave_maps returns it       */
+  const uint64_t *seg_key;       /* [n_segs]; may be NULL when entry_key is                */
+  const int64_t *seg_active;     /* [n_segs], -1 = ::blank                                 */
+  const uint64_t *coll_offsets;  /* HOST [n_colls+1]; read only with a value column        */
+  uint32_t value_size;           /* 0, 1, 2, 4 or 8                                        */
+  const void *value;             /* [N] or NULL, collection-local order                    */
+} cw_map_render_batch;
+
+typedef struct {
+  uint64_t *entry_offsets;       /* HOST [n_colls+1]                                       */
+  uint64_t *entry_key;           /* [n_segs] or NULL                                       */
+  uint32_t *entry_src;           /* [n_segs] or NULL                                       */
+  void *entry_value;             /* [n_segs] elements of value_size, or NULL               */
+} cw_map_render_result;
+
+/* memspace: where seg_coll, seg_key, seg_active, value and the entry arrays
+ * live (coll_offsets and entry_offsets: host memory).  Exactly
+ * entry_offsets[n_colls] elements of each entry array are written.  All three
+ * entry arrays may be NULL (the count-only call).
+ * Errors (< 0, nothing written): as cw_render_lists (coll_offsets is checked
+ * only with a value column; n_segs or n_colls >= 2^32 - 1; with n_segs > 0 a
+ * null seg_coll or seg_active, or a null seg_key while entry_key is asked
+ * for).  A seg_coll that is not ascending or names a collection >= n_colls is
+ * found on the device: the call returns < 0 after its readback, and the
+ * entry arrays (not entry_offsets) then hold unspecified values. */
+int cw_render_maps(cw_ctx *ctx, const cw_map_render_batch *batch, cw_map_render_result *result,
+                   int memspace);
 
 /* ------------------------------------ the distributed giant list (config 5) ---- */
 /* Building blocks for one list spread over several GPUs (cause_amd/giant.py:
