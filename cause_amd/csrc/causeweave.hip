@@ -4398,6 +4398,30 @@ struct PendingEvt {
   double bytes;
 };
 
+// The offsets of a call as uploaded (u32), cached while they repeat and while
+// the scratch buffer they went to has not moved (device_layout).
+struct DevLayout {
+  std::vector<uint64_t> off;   // the host copy: one side's offsets, or a's then b's
+  const void *doff = nullptr;  // ... uploaded to this buffer
+  const void *aux = nullptr;   // ... and the caller's second array to this one (optional)
+  bool fits = false;           // the caller's word about the layout, set after a miss
+  LookBack lb;                 // the look-back words of the kernel that reads the layout
+};
+
+// The pack table of a one-kernel map stage, cached while its key repeats: one
+// or two offset arrays and a word of the caller's (pack_table).
+struct PackTable {
+  std::vector<uint64_t> off;   // the host copy: one side's offsets, or a's then b's
+  std::vector<uint32_t> doc0;  // each pack's first collection, then D
+  uint32_t pk = 0, dmax = 1, key = 0;  // pack size (nodes); most collections in one pack
+  bool ok = false;             // every collection fits a pack: the table is on the device
+  LookBack lb;                 // the stage kernel's look-back words
+  void clear() {
+    off.clear();
+    ok = false;
+  }
+};
+
 }  // namespace
 
 struct cw_ctx {
@@ -4483,53 +4507,23 @@ struct cw_ctx {
     bool ok = false;
   } xfront;
   uint32_t map_fused = 1;          // map_fused: one-kernel map weave of small collections
-  struct MapPacks {                // k_map_pack's pack table, cached by collection layout
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> doc0;
-    uint32_t dbits = 0, pk = 0, dmax = 1;  // (dmax: most collections in one pack)
-    LookBack lb;                   // k_map_pack's look-back words
-    uint64_t maxcoll = 0;          // the largest collection of the cached layout
-    bool ok = false;
+  struct MapPacks : PackTable {    // k_map_pack's pack table, keyed by the collection layout
     bool same = false;             // this call's coll_offsets equal off (set by cw_weave_maps)
     bool verify = false;           // ... taken on trust: compared while the kernel runs
   } mpack;
   uint32_t map_merge_fused = 1;    // map_merge_fused: one-kernel union stage of cw_merge_maps
-  struct MapMerge {                // k_map_union's pack table, cached by the two layouts
-    std::vector<uint64_t> ao, bo;
-    std::vector<uint32_t> doc0;
-    uint32_t pk = 0, dmax = 1;
-    LookBack lb;                   // k_map_union's look-back words
-    bool ok = false;
-  } mmerge;
+  PackTable mmerge;                // k_map_union's pack table, keyed by the two layouts
   uint32_t map_weft_fused = 1;     // map_weft_fused: one-kernel select stage of cw_weft_maps
-  struct MapWeft {                 // k_map_weft's pack table, cached by the layout and site_bits
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> doc0;
-    uint32_t site_bits = 0, pk = 0, dmax = 1;
-    LookBack lb;                   // k_map_weft's look-back words
-    bool ok = false;
-  } mweft;
+  PackTable mweft;                 // k_map_weft's pack table, keyed by the layout and site_bits
   uint32_t list_merge_fused = 1;   // list_merge_fused: one-kernel union stage of cw_merge_lists
-  struct ListMerge {               // the two layouts of the last cw_merge_lists call, as uploaded
-    std::vector<uint64_t> ao, bo;
-    const void *doff = nullptr;    // ... to this buffer
-    bool fits = false;             // every document has na + nb <= LU_MAXDOC
-    LookBack lb;                   // k_list_union's look-back words
-  } lmerge;
+  DevLayout lmerge;                // cw_merge_lists' two layouts (fits: na + nb <= LU_MAXDOC
+                                   // in every document; lb: k_list_union's look-back words)
   uint32_t list_weft_fused = 1;    // list_weft_fused: one-kernel select stage of the list weft
-  struct ListWeft {                // the layout of the last list weft call, as uploaded
-    std::vector<uint64_t> off;
-    const void *doff = nullptr;    // ... to this buffer
-    bool fits = false;             // every document has <= LW_MAXDOC nodes
-    LookBack lb;                   // k_list_weft's look-back words
-  } lweft;
+  DevLayout lweft;                 // the list weft's layout (fits: every document has
+                                   // <= LW_MAXDOC nodes; lb: k_list_weft's look-back words)
   struct Render {                  // cw_render_lists / cw_render_maps (render.hip)
-    struct Layout {                // the offsets of the last call, as uploaded
-      std::vector<uint64_t> off;
-      const void *doff = nullptr;  // ... to this buffer
-      const void *tdoc = nullptr;  // ... and the tiles' first documents to this one
-    } lists, maps;
-    LookBack lb;                   // k_render's look-back words
+    DevLayout lists, maps;         // their layouts (lists.aux: the tiles' first documents)
+    LookBack lb;                   // k_render's look-back words, for both calls
   } render;
 };
 
@@ -4604,15 +4598,17 @@ const uint32_t *read_small(cw_ctx *c, const void *dev, size_t bytes, bool wait =
   return c->pin_small;
 }
 
-// The host-memory form of a list call: the caller's cw_list_result staged in
-// scratch buffers, and copied out afterwards.  Every entry point stages under
-// the same names (hs_*), which holds only while no entry point that stages a
-// result calls another that stages one: cw_weave_lists_k32 calls
-// weave_lists_impl and only the callee stages; cw_merge_lists and cw_weft_lists
-// call weave_lists_device; cw_merge_maps calls weave_maps_impl in device
-// memspace.  Sizes are the superset of what the callers need (max(N, 1) nodes,
-// D + 1 documents).  The optional outputs are present exactly when the
-// caller's are.
+// The host-memory form of a list or map call: the caller's cw_list_result or
+// cw_map_result staged in scratch buffers, and copied out afterwards.  Every
+// entry point stages under the same names (hs_* for lists, hm_* for maps),
+// which holds only while no function that stages a result calls another that
+// stages one: cw_weave_lists_k32 calls weave_lists_impl and only the callee
+// stages; cw_merge_lists and cw_weft_lists call weave_lists_device;
+// cw_merge_maps and cw_weft_maps stage (derived_maps_tail) and call
+// weave_maps_impl in device memspace, which then stages nothing.  Sizes are the
+// superset of what the callers need (lists: max(N, 1) nodes, D + 1 documents;
+// maps: cap_segs + 1 key weaves, N + cap_segs places, D collections).  The
+// optional outputs are present exactly when the caller's are.
 int stage_list_result(cw_ctx *c, const cw_list_result &res, uint64_t N, uint64_t D,
                       cw_list_result *dres) {
   const size_t Ns = std::max<uint64_t>(N, 1);
@@ -4646,6 +4642,91 @@ int unstage_list_result(cw_ctx *c, const cw_list_result &dres, uint64_t N, uint6
   if (res.max_ts) HIPCHK(c, hipMemcpy(res.max_ts, dres.max_ts, D * 8, hipMemcpyDeviceToHost));
   HIPCHK(c, hipMemcpy(res.status, dres.status, D * 4, hipMemcpyDeviceToHost));
   HIPCHK(c, hipDeviceSynchronize());
+  return 0;
+}
+
+// The map twins.  N: the nodes of the woven batch.
+int stage_map_result(cw_ctx *c, const cw_map_result &res, uint64_t N, uint64_t D, cw_map_result *dres) {
+  const uint64_t cap = res.cap_segs;
+  cw_map_result &r = *dres;
+  r = res;
+  r.seg_offsets = scratch_t<uint64_t>(c, "hm_so", cap + 1);
+  r.seg_coll = scratch_t<uint32_t>(c, "hm_sc", cap);
+  r.seg_key = scratch_t<uint64_t>(c, "hm_sk", cap);
+  r.seg_active = scratch_t<int64_t>(c, "hm_sa", cap);
+  r.seg_perm = scratch_t<uint32_t>(c, "hm_sp", N + cap);
+  r.status = scratch_t<uint32_t>(c, "hm_st", D);
+  if (!r.seg_offsets || !r.seg_coll || !r.seg_key || !r.seg_active || !r.seg_perm || !r.status)
+    return fail(c, "out of device memory (host-mode staging)");
+  return 0;
+}
+
+// ... and back: the dres.n_segs key weaves of N nodes and the D collections of
+// the staged result (or of any result in device memory) to the caller's
+// arrays.  Blocking copies: the stream is idle (the caller's wait).
+int unstage_map_result(cw_ctx *c, const cw_map_result &dres, uint64_t N, uint64_t D, cw_map_result &res) {
+  const uint64_t S = dres.n_segs;
+  HIPCHK(c, hipMemcpy(res.seg_perm, dres.seg_perm, (N + S) * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.seg_offsets, dres.seg_offsets, (S + 1) * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.seg_coll, dres.seg_coll, S * 4, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.seg_key, dres.seg_key, S * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.seg_active, dres.seg_active, S * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(res.status, dres.status, D * 4, hipMemcpyDeviceToHost));
+  res.n_segs = S;
+  return 0;
+}
+
+// The offsets of a call on the device as u32[D + 1] -- a's in the scratch buffer
+// name[0]; with bo, b's in name[1] and their sums in name[2] -- cached in `ly`
+// while they repeat and while the buffers have not moved (a scratch buffer
+// that has grown is a miss).  `aux`: the buffer of a second array the caller
+// derives from the offsets, part of the key (or nullptr).  name[] and dev[]
+// have one entry, or three with bo; dev[]: the device copies.  *miss: they were uploaded just now (the stream is idle): the caller
+// sets ly.fits and uploads its second array, and clears ly.off should that fail.
+int device_layout(cw_ctx *c, DevLayout &ly, uint64_t D, const uint64_t *ao, const uint64_t *bo,
+                  const char *const *name, const void *aux, const uint32_t **dev, bool *miss) {
+  const size_t n = D + 1, sides = bo ? 2 : 1;
+  uint32_t *p[3] = {nullptr, nullptr, nullptr};
+  for (size_t k = 0; k < 2 * sides - 1; k++) {
+    p[k] = scratch_t<uint32_t>(c, name[k], n);
+    if (!p[k]) return fail(c, "out of device memory (%s)", name[k]);
+    dev[k] = p[k];
+  }
+  *miss = !(ly.doff == p[0] && ly.aux == aux && ly.off.size() == sides * n &&
+            memcmp(ly.off.data(), ao, n * 8) == 0 && (!bo || memcmp(ly.off.data() + n, bo, n * 8) == 0));
+  if (!*miss) return 0;
+  std::vector<uint32_t> h[3];
+  h[0].assign(ao, ao + n);
+  if (bo) {
+    h[1].assign(bo, bo + n);
+    h[2].resize(n);
+    for (size_t d = 0; d < n; d++) h[2][d] = (uint32_t)(ao[d] + bo[d]);
+  }
+  ly.off.clear();
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (size_t k = 0; k < 2 * sides - 1; k++)
+    HIPCHK(c, hipMemcpy(p[k], h[k].data(), n * 4, hipMemcpyHostToDevice));
+  ly.off.assign(ao, ao + n);
+  if (bo) ly.off.insert(ly.off.end(), bo, bo + n);
+  ly.doff = p[0];
+  ly.aux = aux;
+  return 0;
+}
+
+// After a count pass: the counts of D units (device) scanned on the host into
+// the offsets `off` (host, u64[D + 1]) and `doff` (device, u32[D + 1]) for the
+// write pass.  Waits for the stream.
+int scan_counts(cw_ctx *c, const uint32_t *dcnt, uint64_t D, uint64_t *off, uint32_t *doff) {
+  std::vector<uint32_t> h_cnt(D), h_off(D + 1);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(h_cnt.data(), dcnt, D * 4, hipMemcpyDeviceToHost));
+  off[0] = 0;
+  for (uint64_t d = 0; d < D; d++) {
+    off[d + 1] = off[d] + h_cnt[d];
+    h_off[d] = (uint32_t)off[d];
+  }
+  h_off[D] = (uint32_t)off[D];
+  HIPCHK(c, hipMemcpy(doff, h_off.data(), (D + 1) * 4, hipMemcpyHostToDevice));
   return 0;
 }
 
@@ -4800,6 +4881,60 @@ bool pack_runs(uint64_t D, const uint64_t *ao, const uint64_t *bo, uint64_t pk, 
   }
   doc0.push_back((uint32_t)D);
   return true;
+}
+
+struct PackNames {  // a caller's scratch names: doc0, each pack's first node and the offsets per side
+  const char *doc0, *a0, *b0, *aoff, *boff;
+};
+
+// The pack table of a one-kernel map stage over the collections of `ao` (and
+// `bo`: na + nb nodes a collection), cached in `pt` while ao, bo and `key`
+// repeat (`same`: the caller knows that they do).  The pack size is the
+// smallest of 512 / 1024 / pk_max nodes that holds the largest collection --
+// smaller packs are more workgroups a CU with cheaper barriers (config 4: 2048
+// nodes 3.77 ms, 1024 3.26, 512 3.15; 256 nodes / one wave: 3.95); the kernels'
+// instances are <PK, PK / 4 threads> -- and a pack has at most max_docs
+// collections.  pt.ok: every collection fits a pack, and pt.doc0, each pack's
+// first node per side and the u64 offsets per side are in the buffers `nm`
+// names.  On an error the cache is cleared: the next call builds the table again.
+int pack_table(cw_ctx *c, PackTable &pt, bool same, uint64_t D, const uint64_t *ao, const uint64_t *bo,
+               uint32_t pk_max, uint64_t max_docs, uint32_t key, const PackNames &nm) {
+  const size_t n = D + 1;
+  if (same || (pt.key == key && pt.off.size() == (bo ? 2 : 1) * n && memcmp(pt.off.data(), ao, n * 8) == 0 &&
+               (!bo || memcmp(pt.off.data() + n, bo, n * 8) == 0)))
+    return 0;
+  pt.clear();
+  uint64_t mx = 0;
+  for (uint64_t d = 0; d < D; d++) mx = std::max(mx, (ao[d + 1] - ao[d]) + (bo ? bo[d + 1] - bo[d] : 0));
+  pt.pk = mx <= 512 ? 512u : mx <= 1024 ? 1024u : pk_max;
+  const bool ok = mx <= pk_max && max_docs > 0 && pack_runs(D, ao, bo, pt.pk, max_docs, pt.doc0, &pt.dmax);
+  pt.dmax = std::max(pt.dmax, 1u);
+  if (ok) {
+    const size_t P1 = pt.doc0.size();
+    std::vector<uint64_t> a0(P1), b0(bo ? P1 : 0);
+    for (size_t k = 0; k < P1; k++) {
+      a0[k] = ao[pt.doc0[k]];
+      if (bo) b0[k] = bo[pt.doc0[k]];
+    }
+    uint32_t *dp = scratch_t<uint32_t>(c, nm.doc0, P1);
+    uint64_t *da0 = scratch_t<uint64_t>(c, nm.a0, P1), *dao = scratch_t<uint64_t>(c, nm.aoff, n);
+    uint64_t *db0 = bo ? scratch_t<uint64_t>(c, nm.b0, P1) : nullptr;
+    uint64_t *dbo = bo ? scratch_t<uint64_t>(c, nm.boff, n) : nullptr;
+    if (!dp || !da0 || !dao || (bo && (!db0 || !dbo))) return fail(c, "out of device memory (%s)", nm.doc0);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(dp, pt.doc0.data(), P1 * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(da0, a0.data(), P1 * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dao, ao, n * 8, hipMemcpyHostToDevice));
+    if (bo) {
+      HIPCHK(c, hipMemcpy(db0, b0.data(), P1 * 8, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(dbo, bo, n * 8, hipMemcpyHostToDevice));
+    }
+  }
+  pt.off.assign(ao, ao + n);
+  if (bo) pt.off.insert(pt.off.end(), bo, bo + n);
+  pt.key = key;
+  pt.ok = ok;
+  return 0;
 }
 
 // Host tables: tiles (sort/pass grids), splitter blocks and walker blocks.
@@ -6758,13 +6893,11 @@ struct MapWeave {
 // The collection layout: monotone, every collection below the list limit.
 int maps_check_layout(cw_ctx *c, const cw_map_batch *bt) {
   const uint64_t *o = bt->coll_offsets, D = bt->n_colls;
-  uint64_t back = 0, big = 0, mx = 0;
+  uint64_t back = 0, big = 0;
   for (uint64_t d = 0; d < D; d++) {  // branch-free: vectorizes
     back |= (uint64_t)(o[d + 1] < o[d]);
     big |= (uint64_t)(o[d + 1] - o[d] >= LINK_IDX - 1);
-    mx = std::max<uint64_t>(mx, o[d + 1] - o[d]);
   }
-  c->mpack.maxcoll = mx;
   if (back) return fail(c, "coll_offsets not monotone");
   if (big)
     for (uint64_t d = 0; d < D; d++)
@@ -7030,13 +7163,20 @@ int maps_finish(MapWeave &m) {
   }
   if (check_launch(c, "m_active")) return -1;
 
-  const hipMemcpyKind out_kind = m.dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-  HIPCHK(c, hipMemcpyAsync(res->seg_perm, seg_perm, NL * 4, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_offsets, m.seg_off, (S + 1) * 8, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_coll, m.seg_coll, S * 4, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_key, m.seg_key, S * 8, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->seg_active, seg_act, S * 8, out_kind, c->stream));
-  HIPCHK(c, hipMemcpyAsync(res->status, m.status, m.D * 4, out_kind, c->stream));
+  if (!m.dev) {  // host memory: the general path's own arrays are the staged result
+    cw_map_result own = *res;
+    own.n_segs = S, own.seg_perm = seg_perm, own.seg_offsets = m.seg_off, own.seg_coll = m.seg_coll;
+    own.seg_key = m.seg_key, own.seg_active = seg_act, own.status = m.status;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return unstage_map_result(c, own, m.N, m.D, *res);
+  }
+  const hipMemcpyKind dd = hipMemcpyDeviceToDevice;  // device memory: on the stream
+  HIPCHK(c, hipMemcpyAsync(res->seg_perm, seg_perm, NL * 4, dd, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_offsets, m.seg_off, (S + 1) * 8, dd, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_coll, m.seg_coll, S * 4, dd, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_key, m.seg_key, S * 8, dd, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->seg_active, seg_act, S * 8, dd, c->stream));
+  HIPCHK(c, hipMemcpyAsync(res->status, m.status, m.D * 4, dd, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   res->n_segs = S;
   return 0;
@@ -7177,33 +7317,14 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   }
   // the two layouts and the capacity slots on the device, cached while they repeat
   {
-    auto &lm = c->lmerge;
-    uint32_t *dao = scratch_t<uint32_t>(c, "g_aoff", D + 1), *dbo = scratch_t<uint32_t>(c, "g_boff", D + 1),
-             *dco = scratch_t<uint32_t>(c, "g_coff", D + 1);
-    if (!dao || !dbo || !dco) return fail(c, "out of device memory (merge offsets)");
-    const bool same = lm.doff == dao && lm.ao.size() == D + 1 && lm.bo.size() == D + 1 &&
-                      memcmp(lm.ao.data(), ao, (D + 1) * 8) == 0 &&
-                      memcmp(lm.bo.data(), bo, (D + 1) * 8) == 0;
-    if (!same) {
-      std::vector<uint32_t> h_ao(D + 1), h_bo(D + 1), h_co(D + 1);
-      for (uint64_t d = 0; d <= D; d++) {
-        h_ao[d] = (uint32_t)ao[d];
-        h_bo[d] = (uint32_t)bo[d];
-        h_co[d] = (uint32_t)(ao[d] + bo[d]);
-      }
-      lm.ao.clear();
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(dao, h_ao.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dbo, h_bo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dco, h_co.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-      lm.ao.assign(ao, ao + D + 1);
-      lm.bo.assign(bo, bo + D + 1);
-      lm.doff = dao;
-      lm.fits = dmax <= LU_MAXDOC;
-    }
-    h.a.off = dao;
-    h.b.off = dbo;
-    h.coff = dco;
+    const char *const name[3] = {"g_aoff", "g_boff", "g_coff"};
+    const uint32_t *dev[3];
+    bool miss;
+    if (device_layout(c, c->lmerge, D, ao, bo, name, nullptr, dev, &miss)) return -1;
+    if (miss) c->lmerge.fits = dmax <= LU_MAXDOC;
+    h.a.off = dev[0];
+    h.b.off = dev[1];
+    h.coff = dev[2];
   }
   // the merged documents (device) and the union status
   h.mid = scratch_t<uint64_t>(c, "g_mid", NCs);
@@ -7249,6 +7370,33 @@ int merge_lists_impl(cw_ctx *c, const cw_merge_batch *bt, cw_merge_result *res, 
   return c->prof ? collect_prof(c) : 0;
 }
 
+// What cw_merge_maps and cw_weft_maps end in: the derived collections `mb`
+// (device arrays, host offsets) through weave_maps_impl in device memspace, the
+// stage's status words `extra` joined to the weave's bits (nullptr: the stage
+// wrote none), and in host memspace the result `M` staged before and copied
+// out after, with the stage's source indices `dsrc` to `hsrc`.
+int derived_maps_tail(cw_ctx *c, const cw_map_batch &mb, cw_map_result &M, bool dev, const uint32_t *extra,
+                      const uint32_t *dsrc, uint32_t *hsrc) {
+  const uint64_t D = mb.n_colls, N = mb.coll_offsets[D];
+  cw_map_result mr = M;
+  if (!dev && stage_map_result(c, M, N, D, &mr)) return -1;
+  if (weave_maps_impl(c, &mb, &mr, CW_MEM_DEVICE)) return -1;
+  M.n_segs = mr.n_segs;
+  if (extra) {
+    hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, extra,
+                       mr.status, (uint32_t)D);
+    if (check_launch(c, "or_status")) return -1;
+  }
+  if (!dev) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(hsrc, dsrc, N * 4, hipMemcpyDeviceToHost));
+    if (unstage_map_result(c, mr, N, D, M)) return -1;
+  } else if (!c->async) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return c->prof ? collect_prof(c) : 0;
+}
+
 // cw_merge_maps: uploads (host memspace), the union stage (mapmerge.hip), one
 // device-to-host copy of the merged offsets, weave_maps_impl in device memspace
 // on the merged arrays, copies out.  The merged arrays have scratch names of
@@ -7267,7 +7415,6 @@ int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result
       (Nb && (!bt->b.id_key || !bt->b.cause || !bt->b.cause_is_id || !bt->b.kind || !bt->b_value)))
     return fail(c, "null input arrays");
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t cap = M.cap_segs;
   uint64_t *mo = res->merged_offsets;
   MuHost h{};
   h.D = D;
@@ -7308,49 +7455,9 @@ int merge_maps_impl(cw_ctx *c, const cw_map_merge_batch *bt, cw_map_merge_result
     if (rc == 1) rc = map_union_general(c, h, mo);  // one oversize collection: the whole call
     if (rc) return -1;
   }
-  const uint64_t NM = mo[D];
-  // the map reweave of the merged collections, in device memory
-  cw_map_batch mb{};
-  mb.n_colls = D;
-  mb.coll_offsets = mo;
-  mb.id_key = mid;
-  mb.cause = mca;
-  mb.cause_is_id = mcis;
-  mb.kind = mkd;
-  mb.key_bits = bt->a.key_bits;
-  mb.token_bits = bt->a.token_bits;
-  cw_map_result mr = M;
-  if (!dev) {
-    mr.seg_offsets = scratch_t<uint64_t>(c, "mm_so", cap + 1);
-    mr.seg_coll = scratch_t<uint32_t>(c, "mm_sc", cap);
-    mr.seg_key = scratch_t<uint64_t>(c, "mm_sk", cap);
-    mr.seg_active = scratch_t<int64_t>(c, "mm_sa", cap);
-    mr.seg_perm = scratch_t<uint32_t>(c, "mm_sp", NM + cap);
-    mr.status = scratch_t<uint32_t>(c, "mm_st", D);
-    if (!mr.seg_offsets || !mr.seg_coll || !mr.seg_key || !mr.seg_active || !mr.seg_perm || !mr.status)
-      return fail(c, "out of device memory (map merge outputs)");
-  }
-  if (weave_maps_impl(c, &mb, &mr, CW_MEM_DEVICE)) return -1;
-  M.n_segs = mr.n_segs;
-  if (NC && D) {  // the union's DUP / ORPHAN join the weave's bits
-    hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, ust,
-                       mr.status, (uint32_t)D);
-    if (check_launch(c, "or_status")) return -1;
-  }
-  if (!dev) {
-    const uint64_t S = mr.n_segs;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(res->merged_src, msrc, NM * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_perm, mr.seg_perm, (NM + S) * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_offsets, mr.seg_offsets, (S + 1) * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_coll, mr.seg_coll, S * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_key, mr.seg_key, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_active, mr.seg_active, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.status, mr.status, D * 4, hipMemcpyDeviceToHost));
-  } else if (!c->async) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return c->prof ? collect_prof(c) : 0;
+  // the map reweave of the merged collections; the union's DUP / ORPHAN join the weave's bits
+  const cw_map_batch mb{D, mo, mid, mca, mcis, mkd, bt->a.key_bits, bt->a.token_bits};
+  return derived_maps_tail(c, mb, M, dev, NC && D ? ust : nullptr, msrc, res->merged_src);
 }
 
 // cw_weft_maps: uploads (host memspace), the select stage (mapweft.hip), one
@@ -7382,7 +7489,6 @@ int weft_maps_impl(cw_ctx *c, const cw_map_weft_batch *bt, cw_map_weft_result *r
     return fail(c, "weft too large: %llu nodes and cut slots (limit 2^32-2)", (unsigned long long)(N + NS));
   if (N && (!B.id_key || !B.cause || !B.cause_is_id || !B.kind)) return fail(c, "null input arrays");
   HIPCHK(c, hipSetDevice(c->device));
-  const uint64_t cap = M.cap_segs;
   uint64_t *ko = res->kept_offsets;
   MwHost h{};
   h.D = D;
@@ -7413,49 +7519,10 @@ int weft_maps_impl(cw_ctx *c, const cw_map_weft_batch *bt, cw_map_weft_result *r
     if (rc == 1) rc = map_weft_general(c, h, ko);  // one oversize collection: the whole call
     if (rc) return -1;
   }
-  const uint64_t NK = ko[D];
-  // the map reweave of the kept collections, in device memory
-  cw_map_batch mb{};
-  mb.n_colls = D;
-  mb.coll_offsets = ko;
-  mb.id_key = kid;
-  mb.cause = kca;
-  mb.cause_is_id = kcis;
-  mb.kind = kkd;
-  mb.key_bits = B.key_bits;
-  mb.token_bits = B.token_bits;
-  cw_map_result mr = M;
-  if (!dev) {
-    mr.seg_offsets = scratch_t<uint64_t>(c, "mw_so", cap + 1);
-    mr.seg_coll = scratch_t<uint32_t>(c, "mw_sc", cap);
-    mr.seg_key = scratch_t<uint64_t>(c, "mw_sk", cap);
-    mr.seg_active = scratch_t<int64_t>(c, "mw_sa", cap);
-    mr.seg_perm = scratch_t<uint32_t>(c, "mw_sp", NK + cap);
-    mr.status = scratch_t<uint32_t>(c, "mw_st", D);
-    if (!mr.seg_offsets || !mr.seg_coll || !mr.seg_key || !mr.seg_active || !mr.seg_perm || !mr.status)
-      return fail(c, "out of device memory (map weft outputs)");
-  }
-  if (weave_maps_impl(c, &mb, &mr, CW_MEM_DEVICE)) return -1;
-  M.n_segs = mr.n_segs;
-  if (D) {  // the collections that got an [id] node: WEFT joins the weave's bits
-    hipLaunchKernelGGL(k_or_status, dim3((uint32_t)((D + 255) / 256)), dim3(256), 0, c->stream, wst,
-                       mr.status, (uint32_t)D);
-    if (check_launch(c, "or_status")) return -1;
-  }
-  if (!dev) {
-    const uint64_t S = mr.n_segs;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(res->kept_src, ksrc, NK * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_perm, mr.seg_perm, (NK + S) * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_offsets, mr.seg_offsets, (S + 1) * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_coll, mr.seg_coll, S * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_key, mr.seg_key, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.seg_active, mr.seg_active, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(M.status, mr.status, D * 4, hipMemcpyDeviceToHost));
-  } else if (!c->async) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return c->prof ? collect_prof(c) : 0;
+  // the map reweave of the kept collections; the collections that got an [id]
+  // node: WEFT joins the weave's bits
+  const cw_map_batch mb{D, ko, kid, kca, kcis, kkd, B.key_bits, B.token_bits};
+  return derived_maps_tail(c, mb, M, dev, D ? wst : nullptr, ksrc, res->kept_src);
 }
 
 // cw_weft_lists / cw_weft_lists_dev: uploads (host memspace), the select stage
@@ -7643,8 +7710,7 @@ int cw_ctx_set_option(cw_ctx *c, const char *name, uint32_t value) {
     // what was derived from the options is cached by layout alone: the
     // document tables (tour, splitter blocks, slot sizes) and the map packs
     c->tab_on_device = false;
-    c->mpack.ok = false;
-    c->mpack.off.clear();
+    c->mpack.clear();
     return 0;
   }
   return fail(c, "unknown option %s", name);

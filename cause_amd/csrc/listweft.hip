@@ -199,20 +199,10 @@ struct LwHost {  // what weft_lists_impl hands the select stage (device pointers
 // the fused kernel, cached in the context while doc_offsets repeats.  `largest`:
 // the largest document (check_doc_offsets).
 int list_weft_layout(cw_ctx *c, const uint64_t *off, uint64_t D, uint64_t largest, const uint32_t **doff) {
-  auto &lw = c->lweft;
-  uint32_t *p = scratch_t<uint32_t>(c, "w_off", D + 1);
-  if (!p) return fail(c, "out of device memory (weft offsets)");
-  const bool same = lw.doff == p && lw.off.size() == D + 1 && memcmp(lw.off.data(), off, (D + 1) * 8) == 0;
-  if (!same) {
-    const std::vector<uint32_t> h_off(off, off + D + 1);
-    lw.off.clear();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(p, h_off.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-    lw.off.assign(off, off + D + 1);
-    lw.doff = p;
-    lw.fits = largest <= LW_MAXDOC;
-  }
-  *doff = p;
+  const char *name = "w_off";
+  bool miss;
+  if (device_layout(c, c->lweft, D, off, nullptr, &name, nullptr, doff, &miss)) return -1;
+  if (miss) c->lweft.fits = largest <= LW_MAXDOC;
   return 0;
 }
 
@@ -267,16 +257,7 @@ int list_weft_general(cw_ctx *c, LwHost &h, uint64_t *ko) {
   };
   // ids twice, a cut word three times and the kind per node; the cut slots once
   if (select("weft_count", 0, (double)h.N * 41 + (double)(D << sb) * 8 + (double)D * 16)) return -1;
-  std::vector<uint32_t> h_cnt(D), h_ko(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), kcnt, D * 4, hipMemcpyDeviceToHost));
-  ko[0] = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    ko[d + 1] = ko[d] + h_cnt[d];
-    h_ko[d] = (uint32_t)ko[d];
-  }
-  h_ko[D] = (uint32_t)ko[D];
-  HIPCHK(c, hipMemcpy(koff, h_ko.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  if (scan_counts(c, kcnt, D, ko, koff)) return -1;
   return select("weft_write", 1,
                 (double)h.N * 41 + (double)(D << sb) * 8 + (double)D * 12 + (double)ko[D] * 30);
 }

@@ -331,16 +331,7 @@ int union_sort_dedup(cw_ctx *c, const UnionNames &nm, const UnionCat &cat, uint6
     return check_launch(c, stat);
   };
   if (dedup(nm.count, 0, (double)NC * 12)) return -1;
-  std::vector<uint32_t> h_cnt(D), h_mo(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), mcnt, D * 4, hipMemcpyDeviceToHost));
-  mo[0] = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    mo[d + 1] = mo[d] + h_cnt[d];
-    h_mo[d] = (uint32_t)mo[d];
-  }
-  h_mo[D] = (uint32_t)mo[D];
-  HIPCHK(c, hipMemcpy(dmo, h_mo.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  if (scan_counts(c, mcnt, D, mo, dmo)) return -1;
   if (dedup(nm.write, 1, (double)NC * 12 + (double)mo[D] * 21)) return -1;
   *dmo_out = dmo;
   return 0;
@@ -362,39 +353,9 @@ struct MuHost {  // what merge_maps_impl hands the union stage (device pointers)
 int map_union_fused(cw_ctx *c, MuHost &h, uint64_t *mo) {
   const uint64_t D = h.D, *ao = h.ao, *bo = h.bo;
   auto &mm = c->mmerge;
-  const bool same = mm.ao.size() == D + 1 && mm.bo.size() == D + 1 &&
-                    memcmp(mm.ao.data(), ao, (D + 1) * 8) == 0 &&
-                    memcmp(mm.bo.data(), bo, (D + 1) * 8) == 0;
-  if (!same) {  // pack table, cached while both layouts repeat
-    mm.ao.assign(ao, ao + D + 1);
-    mm.bo.assign(bo, bo + D + 1);
-    uint64_t mx = 0;
-    for (uint64_t d = 0; d < D; d++) mx = std::max(mx, (ao[d + 1] - ao[d]) + (bo[d + 1] - bo[d]));
-    mm.pk = map_pack_size(mx);
-    mm.ok = mx <= MPK && pack_runs(D, ao, bo, mm.pk, MU_MAXCOLL, mm.doc0, &mm.dmax);
-    mm.dmax = std::max(mm.dmax, 1u);
-    if (mm.ok) {
-      const size_t P1 = mm.doc0.size();
-      std::vector<uint64_t> pa(P1), pb(P1);
-      for (size_t k = 0; k < P1; k++) {
-        pa[k] = ao[mm.doc0[k]];
-        pb[k] = bo[mm.doc0[k]];
-      }
-      uint32_t *dp = scratch_t<uint32_t>(c, "mm_doc0", P1);
-      uint64_t *dpa = scratch_t<uint64_t>(c, "mm_pa0", P1), *dpb = scratch_t<uint64_t>(c, "mm_pb0", P1);
-      uint64_t *dao = scratch_t<uint64_t>(c, "mm_aoff", D + 1), *dbo = scratch_t<uint64_t>(c, "mm_boff", D + 1);
-      if (!dp || !dpa || !dpb || !dao || !dbo) {
-        mm.ao.clear();
-        return fail(c, "out of device memory (map merge packs)");
-      }
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(dp, mm.doc0.data(), P1 * 4, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dpa, pa.data(), P1 * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dpb, pb.data(), P1 * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dao, ao, (D + 1) * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dbo, bo, (D + 1) * 8, hipMemcpyHostToDevice));
-    }
-  }
+  if (pack_table(c, mm, false, D, ao, bo, MPK, MU_MAXCOLL, 0,
+                 PackNames{"mm_doc0", "mm_pa0", "mm_pb0", "mm_aoff", "mm_boff"}))
+    return -1;
   if (!mm.ok) return 1;
   const uint32_t P = (uint32_t)mm.doc0.size() - 1;
   const uint64_t NC = h.Na + h.Nb;
@@ -440,8 +401,7 @@ int map_union_general(cw_ctx *c, MuHost &h, uint64_t *mo) {
   uint8_t *ckd = scratch_t<uint8_t>(c, "mm_ckd", NC);
   if (!dao || !dbo || !dco || !cid || !cca || !cva || !ckd)
     return fail(c, "out of device memory (map merge, N=%llu)", (unsigned long long)NC);
-  c->mmerge.ao.clear();  // (mm_aoff / mm_boff are rewritten: the fused route's cache is void)
-  c->mmerge.bo.clear();
+  c->mmerge.clear();  // (mm_aoff / mm_boff are rewritten: the fused route's cache is void)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(dao, ao, (D + 1) * 8, hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(dbo, bo, (D + 1) * 8, hipMemcpyHostToDevice));

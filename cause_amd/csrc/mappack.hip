@@ -708,12 +708,6 @@ __global__ __launch_bounds__(NT) void k_map_pack(
 
 namespace {
 
-// Pack size: the smallest of 512 / 1024 / 2048 nodes that holds the largest
-// collection -- smaller packs are more workgroups a CU with cheaper barriers
-// (config 4: 2048 nodes 3.77 ms, 1024 3.26, 512 3.15; 256 nodes / one wave:
-// 3.95).  The kernels' instances are <PK, PK / 4 threads>.
-uint32_t map_pack_size(uint64_t largest) { return largest <= 512 ? 512u : largest <= 1024 ? 1024u : MPK; }
-
 // One launch of a kernel template <PK, NT> at the pack size pk.
 #define CW_PK_LAUNCH(KERN, pk, P, dyn, stream, ...)                                              \
   do {                                                                                           \
@@ -733,47 +727,18 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
                       const uint8_t *kind) {
   const uint64_t D = bt->n_colls, *off = bt->coll_offsets;
   const uint32_t N = (uint32_t)off[D];
-  // pack table, cached while the collection layout repeats
-  auto &pc = c->mpack;
-  const uint32_t PKN = map_pack_size(pc.maxcoll);
-  if (!(pc.pk == PKN && pc.same)) {
-    pc.off.assign(off, off + D + 1);
-    pc.pk = PKN;
-    pc.ok = pack_runs(D, off, nullptr, PKN, D, pc.doc0, &pc.dmax);  // (false: a collection of more than MPK nodes)
-    pc.dmax = std::max(pc.dmax, 1u);
-    pc.dbits = ceil_log2(pc.dmax);
-    if (pc.ok) {
-      uint32_t *dp = scratch_t<uint32_t>(c, "mp_doc0", pc.doc0.size());
-      uint64_t *dof = scratch_t<uint64_t>(c, "mp_off", D + 1);
-      uint64_t *ds0 = scratch_t<uint64_t>(c, "mp_s0", pc.doc0.size());  // each pack's first node
-      if (!dp || !dof) return fail(c, "out of device memory (map packs)");
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(dp, pc.doc0.data(), pc.doc0.size() * 4, hipMemcpyHostToDevice));
-      std::vector<uint64_t> s0(pc.doc0.size());
-      for (size_t k = 0; k < s0.size(); k++) s0[k] = off[pc.doc0[k]];
-      if (!ds0) return fail(c, "out of device memory (map packs)");
-      HIPCHK(c, hipMemcpy(ds0, s0.data(), s0.size() * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dof, off, (D + 1) * 8, hipMemcpyHostToDevice));
-    }
-  }
+  auto &pc = c->mpack;  // (pc.same: maps_check compared the layout, or takes it on trust)
+  if (pack_table(c, pc, pc.same, D, off, nullptr, MPK, D, 0,
+                 PackNames{"mp_doc0", "mp_s0", nullptr, "mp_off", nullptr}))
+    return -1;
   if (!pc.ok) return 1;
   const uint32_t P = (uint32_t)pc.doc0.size() - 1;
   const uint64_t cap = res->cap_segs;
   uint32_t *ctl = scratch_t<uint32_t>(c, "mp_ctl", 4);
   if (!ctl) return fail(c, "out of device memory (map packs)");
   // outputs: the caller's arrays (device memory) or staging (host memory)
-  uint64_t *so = res->seg_offsets, *sk = res->seg_key;
-  uint32_t *sc = res->seg_coll, *sp = res->seg_perm, *st = res->status;
-  int64_t *sa = res->seg_active;
-  if (!dev) {
-    so = scratch_t<uint64_t>(c, "mp_so", cap + 1);
-    sk = scratch_t<uint64_t>(c, "mp_sk", cap);
-    sc = scratch_t<uint32_t>(c, "mp_sc", cap);
-    sp = scratch_t<uint32_t>(c, "mp_sp", N + cap);
-    st = scratch_t<uint32_t>(c, "mp_st", D);
-    sa = scratch_t<int64_t>(c, "mp_sa", cap);
-    if (!so || !sk || !sc || !sp || !st || !sa) return fail(c, "out of device memory (map outputs)");
-  }
+  cw_map_result out = *res;
+  if (!dev && stage_map_result(c, *res, N, D, &out)) return -1;
   unsigned long long *tprof = nullptr;
   if (c->tree_prof && alloc_stamps(c, "mp_tprof", P, 8, &tprof)) return -1;
   uint32_t epoch;
@@ -786,8 +751,8 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
     Launch L(c, "m_pack", (double)N * (8 + 8 + 1 + 1 + 4) + (double)N * 0.42 * (4 + 8 + 4 + 8 + 8));
     CW_PK_LAUNCH(k_map_pack, pc.pk, P, (size_t)(2 * pc.dmax + 1) * 4, c->stream, id, cause, cis, kind,
                  (const uint64_t *)c->bufs["mp_off"].p, (const uint32_t *)c->bufs["mp_doc0"].p,
-                 (const uint64_t *)c->bufs["mp_s0"].p, P, bt->token_bits, lb, cap, (uint64_t)N, so, sc, sk,
-                 sa, sp, st, ctl, tprof, pc.dmax, epoch);
+                 (const uint64_t *)c->bufs["mp_s0"].p, P, bt->token_bits, lb, cap, (uint64_t)N, out.seg_offsets,
+                 out.seg_coll, out.seg_key, out.seg_active, out.seg_perm, out.status, ctl, tprof, pc.dmax, epoch);
   }
   if (check_launch(c, "map_pack")) return -1;
   if (pc.verify &&
@@ -806,15 +771,8 @@ int weave_maps_packed(cw_ctx *c, const cw_map_batch *bt, cw_map_result *res, boo
             "outputs %.0f\n", a[0] / P, a[1] / P, a[2] / P, (a[4] + a[6] + a[7]) / P, a[6] / P, a[7] / P,
             a[3] / P, a[5] / P);
   }
-  if (!dev) {
-    HIPCHK(c, hipMemcpy(res->seg_perm, sp, ((size_t)N + S) * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->seg_offsets, so, (S + 1) * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->seg_coll, sc, S * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->seg_key, sk, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->seg_active, sa, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(res->status, st, D * 4, hipMemcpyDeviceToHost));
-  }
-  res->n_segs = S;
+  out.n_segs = res->n_segs = S;
+  if (!dev && unstage_map_result(c, out, N, D, *res)) return -1;  // (the stream is idle: read_small's wait)
   if (c->prof) return collect_prof(c);
   return 0;
 }

@@ -291,34 +291,10 @@ int map_weft_fused(cw_ctx *c, MwHost &h, uint64_t *ko) {
   const uint64_t D = h.D, *off = h.off;
   const uint32_t sb = h.in.site_bits;
   auto &mw = c->mweft;
-  const bool same = mw.site_bits == sb && mw.off.size() == D + 1 &&
-                    memcmp(mw.off.data(), off, (D + 1) * 8) == 0;
-  if (!same) {  // pack table, cached while the layout and site_bits repeat
-    mw.off.assign(off, off + D + 1);
-    mw.site_bits = sb;
-    uint64_t mx = 0;
-    for (uint64_t d = 0; d < D; d++) mx = std::max(mx, off[d + 1] - off[d]);
-    mw.pk = map_pack_size(mx);
-    // (a pack's collections << site_bits stay within the found bits)
-    const uint64_t max_colls = std::min<uint64_t>(MW_MAXCOLL, MW_SLOTS >> sb);
-    mw.ok = mx <= MPK && max_colls > 0 && pack_runs(D, off, nullptr, mw.pk, max_colls, mw.doc0, &mw.dmax);
-    mw.dmax = std::max(mw.dmax, 1u);
-    if (mw.ok) {
-      const size_t P1 = mw.doc0.size();
-      std::vector<uint64_t> s0(P1);
-      for (size_t k = 0; k < P1; k++) s0[k] = off[mw.doc0[k]];
-      uint32_t *dp = scratch_t<uint32_t>(c, "mw_doc0", P1);
-      uint64_t *ds0 = scratch_t<uint64_t>(c, "mw_s0", P1), *dof = scratch_t<uint64_t>(c, "mw_off", D + 1);
-      if (!dp || !ds0 || !dof) {
-        mw.off.clear();
-        return fail(c, "out of device memory (map weft packs)");
-      }
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipMemcpy(dp, mw.doc0.data(), P1 * 4, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(ds0, s0.data(), P1 * 8, hipMemcpyHostToDevice));
-      HIPCHK(c, hipMemcpy(dof, off, (D + 1) * 8, hipMemcpyHostToDevice));
-    }
-  }
+  // (a pack's collections << site_bits stay within the found bits)
+  if (pack_table(c, mw, false, D, off, nullptr, MPK, std::min<uint64_t>(MW_MAXCOLL, MW_SLOTS >> sb), sb,
+                 PackNames{"mw_doc0", "mw_s0", nullptr, "mw_off", nullptr}))
+    return -1;
   if (!mw.ok) return 1;
   const uint32_t P = (uint32_t)mw.doc0.size() - 1;
   uint64_t *dko = scratch_t<uint64_t>(c, "mw_koff", D + 1);
@@ -354,7 +330,7 @@ int map_weft_general(cw_ctx *c, MwHost &h, uint64_t *ko) {
   uint64_t *dof = scratch_t<uint64_t>(c, "mw_off", D + 1);
   uint32_t *kcnt = scratch_t<uint32_t>(c, "mw_kcnt", D), *koff = scratch_t<uint32_t>(c, "mw_koff32", D + 1);
   if (!dof || !kcnt || !koff) return fail(c, "out of device memory (map weft)");
-  c->mweft.off.clear();  // (mw_off is rewritten: the fused route's cache is void)
+  c->mweft.clear();  // (mw_off is rewritten: the fused route's cache is void)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(dof, h.off, (D + 1) * 8, hipMemcpyHostToDevice));
   h.in.off = dof;
@@ -368,16 +344,7 @@ int map_weft_general(cw_ctx *c, MwHost &h, uint64_t *ko) {
   };
   // ids and their cut words twice, the cut slots once
   if (select("mw_count", 0, (double)h.N * 32 + (double)(D << sb) * 8 + (double)D * 24)) return -1;
-  std::vector<uint32_t> h_cnt(D), h_ko(D + 1);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  HIPCHK(c, hipMemcpy(h_cnt.data(), kcnt, D * 4, hipMemcpyDeviceToHost));
-  ko[0] = 0;
-  for (uint64_t d = 0; d < D; d++) {
-    ko[d + 1] = ko[d] + h_cnt[d];
-    h_ko[d] = (uint32_t)ko[d];
-  }
-  h_ko[D] = (uint32_t)ko[D];
-  HIPCHK(c, hipMemcpy(koff, h_ko.data(), (D + 1) * 4, hipMemcpyHostToDevice));
+  if (scan_counts(c, kcnt, D, ko, koff)) return -1;
   return select("mw_write", 1,
                 (double)h.N * 32 + (double)(D << sb) * 8 + (double)D * 20 + (double)ko[D] * 22);
 }

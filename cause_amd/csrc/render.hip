@@ -319,35 +319,25 @@ void render_launch(cw_ctx *c, const RnHost &h, uint32_t tiles) {
 // The layout on the device, cached in the context while the offsets repeat:
 // doc_off (u32[D + 1]) and, for lists, tile_doc[t] = the last document that
 // starts at or below position t * RN_TILE (u32[tiles + 1]).
-int render_layout(cw_ctx *c, cw_ctx::Render::Layout &ly, const char *n_off, const char *n_td,
-                  const uint64_t *off, uint64_t D, uint32_t tiles, bool want_td, const uint32_t **doff,
-                  const uint32_t **tdoc) {
-  uint32_t *p = scratch_t<uint32_t>(c, n_off, D + 1);
+int render_layout(cw_ctx *c, DevLayout &ly, const char *n_off, const char *n_td, const uint64_t *off,
+                  uint64_t D, uint32_t tiles, bool want_td, const uint32_t **doff, const uint32_t **tdoc) {
   uint32_t *q = want_td ? scratch_t<uint32_t>(c, n_td, (size_t)tiles + 1) : nullptr;
-  if (!p || (want_td && !q)) return fail(c, "out of device memory (render offsets)");
-  const bool same = ly.doff == p && ly.tdoc == q && ly.off.size() == D + 1 &&
-                    memcmp(ly.off.data(), off, (D + 1) * 8) == 0;
-  if (!same) {
-    const std::vector<uint32_t> h_off(off, off + D + 1);
-    std::vector<uint32_t> h_td;
-    if (want_td) {
-      h_td.resize((size_t)tiles + 1);
-      uint64_t d = 0;
-      for (uint32_t t = 0; t <= tiles; t++) {
-        const uint64_t g = (uint64_t)t * RN_TILE;
-        while (d + 1 < D && off[d + 1] <= g) d++;
-        h_td[t] = (uint32_t)d;
-      }
+  if (want_td && !q) return fail(c, "out of device memory (render offsets)");
+  bool miss;
+  if (device_layout(c, ly, D, off, nullptr, &n_off, q, doff, &miss)) return -1;
+  if (miss && want_td) {
+    std::vector<uint32_t> h_td((size_t)tiles + 1);
+    uint64_t d = 0;
+    for (uint32_t t = 0; t <= tiles; t++) {
+      const uint64_t g = (uint64_t)t * RN_TILE;
+      while (d + 1 < D && off[d + 1] <= g) d++;
+      h_td[t] = (uint32_t)d;
     }
-    ly.off.clear();
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(p, h_off.data(), (D + 1) * 4, hipMemcpyHostToDevice));
-    if (want_td) HIPCHK(c, hipMemcpy(q, h_td.data(), h_td.size() * 4, hipMemcpyHostToDevice));
-    ly.off.assign(off, off + D + 1);
-    ly.doff = p;
-    ly.tdoc = q;
+    if (hipMemcpy(q, h_td.data(), h_td.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      ly.off.clear();
+      return fail(c, "hipMemcpy (%s)", n_td);
+    }
   }
-  *doff = p;
   *tdoc = q;
   return 0;
 }
