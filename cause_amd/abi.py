@@ -43,23 +43,24 @@ def narrow_k32(id_key, cause_key):
     return out[0], out[1]
 
 
+_U64P = C.POINTER(C.c_uint64)
+# the fields every list batch starts with, and the key layout of the K64 / K32 ones
+_NODES = [("n_docs", C.c_uint64), ("doc_offsets", _U64P), ("id_key", C.c_void_p),
+          ("cause_key", C.c_void_p), ("kind", C.c_void_p)]
+_LAYOUT = [("key_bits", C.c_uint32), ("ts_shift", C.c_uint32), ("site_shift", C.c_uint32),
+           ("site_bits", C.c_uint32)]
+
+
 class CwListBatch(C.Structure):
-    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", C.POINTER(C.c_uint64)),
-                ("id_key", C.c_void_p), ("cause_key", C.c_void_p), ("kind", C.c_void_p),
-                ("key_bits", C.c_uint32), ("ts_shift", C.c_uint32), ("site_shift", C.c_uint32),
-                ("site_bits", C.c_uint32)]
+    _fields_ = _NODES + _LAYOUT
 
 
 class CwListBatchK32(C.Structure):
-    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", C.POINTER(C.c_uint64)),
-                ("id_key", C.c_void_p), ("cause_key", C.c_void_p), ("kind", C.c_void_p),
-                ("key_bits", C.c_uint32), ("ts_shift", C.c_uint32), ("site_shift", C.c_uint32),
-                ("site_bits", C.c_uint32), ("perm16", C.c_uint32)]
+    _fields_ = _NODES + _LAYOUT + [("perm16", C.c_uint32)]
 
 
 class CwListBatchK128(C.Structure):
-    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", C.POINTER(C.c_uint64)),
-                ("id_key", C.c_void_p), ("cause_key", C.c_void_p), ("kind", C.c_void_p)]
+    _fields_ = _NODES
 
 
 class CwListResult(C.Structure):
@@ -69,7 +70,7 @@ class CwListResult(C.Structure):
 
 
 class CwMapBatch(C.Structure):
-    _fields_ = [("n_colls", C.c_uint64), ("coll_offsets", C.POINTER(C.c_uint64)),
+    _fields_ = [("n_colls", C.c_uint64), ("coll_offsets", _U64P),
                 ("id_key", C.c_void_p), ("cause", C.c_void_p), ("cause_is_id", C.c_void_p),
                 ("kind", C.c_void_p), ("key_bits", C.c_uint32), ("token_bits", C.c_uint32)]
 
@@ -86,8 +87,7 @@ class CwMergeBatch(C.Structure):
 
 
 class CwMergeResult(C.Structure):
-    _fields_ = [("merged_offsets", C.POINTER(C.c_uint64)), ("merged_src", C.c_void_p),
-                ("weave", CwListResult)]
+    _fields_ = [("merged_offsets", _U64P), ("merged_src", C.c_void_p), ("weave", CwListResult)]
 
 
 class CwMapMergeBatch(C.Structure):
@@ -96,17 +96,15 @@ class CwMapMergeBatch(C.Structure):
 
 
 class CwMapMergeResult(C.Structure):
-    _fields_ = [("merged_offsets", C.POINTER(C.c_uint64)), ("merged_src", C.c_void_p),
-                ("maps", CwMapResult)]
+    _fields_ = [("merged_offsets", _U64P), ("merged_src", C.c_void_p), ("maps", CwMapResult)]
 
 
 class CwWeftBatch(C.Structure):
-    _fields_ = [("nodes", CwListBatch), ("cut", C.POINTER(C.c_uint64))]
+    _fields_ = [("nodes", CwListBatch), ("cut", _U64P)]
 
 
 class CwWeftResult(C.Structure):
-    _fields_ = [("kept_offsets", C.POINTER(C.c_uint64)), ("kept_src", C.c_void_p),
-                ("weave", CwListResult)]
+    _fields_ = [("kept_offsets", _U64P), ("kept_src", C.c_void_p), ("weave", CwListResult)]
 
 
 class CwMapWeftBatch(C.Structure):
@@ -115,30 +113,29 @@ class CwMapWeftBatch(C.Structure):
 
 
 class CwMapWeftResult(C.Structure):
-    _fields_ = [("kept_offsets", C.POINTER(C.c_uint64)), ("kept_src", C.c_void_p),
-                ("maps", CwMapResult)]
+    _fields_ = [("kept_offsets", _U64P), ("kept_src", C.c_void_p), ("maps", CwMapResult)]
 
 
 class CwRenderBatch(C.Structure):
-    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", C.POINTER(C.c_uint64)),
+    _fields_ = [("n_docs", C.c_uint64), ("doc_offsets", _U64P),
                 ("weave_perm", C.c_void_p), ("visible_bits", C.c_void_p), ("perm16", C.c_uint32),
                 ("value_size", C.c_uint32), ("value", C.c_void_p)]
 
 
 class CwRenderResult(C.Structure):
-    _fields_ = [("rendered_offsets", C.POINTER(C.c_uint64)), ("rendered_src", C.c_void_p),
+    _fields_ = [("rendered_offsets", _U64P), ("rendered_src", C.c_void_p),
                 ("rendered_value", C.c_void_p)]
 
 
 class CwMapRenderBatch(C.Structure):
     _fields_ = [("n_colls", C.c_uint64), ("n_segs", C.c_uint64), ("seg_coll", C.c_void_p),
                 ("seg_key", C.c_void_p), ("seg_active", C.c_void_p),
-                ("coll_offsets", C.POINTER(C.c_uint64)), ("value_size", C.c_uint32),
+                ("coll_offsets", _U64P), ("value_size", C.c_uint32),
                 ("value", C.c_void_p)]
 
 
 class CwMapRenderResult(C.Structure):
-    _fields_ = [("entry_offsets", C.POINTER(C.c_uint64)), ("entry_key", C.c_void_p),
+    _fields_ = [("entry_offsets", _U64P), ("entry_key", C.c_void_p),
                 ("entry_src", C.c_void_p), ("entry_value", C.c_void_p)]
 
 
@@ -150,21 +147,82 @@ class CwLinkedList(C.Structure):
     _fields_ = [("n", C.c_uint64), ("succ", C.c_void_p), ("thr", C.c_void_p), ("val", C.c_void_p)]
 
 
-# the distributed tree's building blocks (include/causeweave.h, dist.hip):
-# argument types after the context
-_DIST_ARGS = {
-    "check": "U64 U32 P P P", "eff": "U64 U32 P P P", "climb": "U64 U32 P P P U64 P",
-    "pending": "P U64 P P", "gkey": "P P U64 P", "runs": "P P U64 U32 P P P P",
-    "rkey": "P U64 P", "link": "P P U64 P U32 U64 P P P", "put": "P P U64 U32 U64 P",
-    "thr": "P U64 U32 P", "succ": "P P P U64 U32 P",
-    "rs_rulers": "P P U64 U32 U32 U32 P P P", "rs_walk": "P U64 P U32 P P U64 U32 P P P P P P",
-    "rs_top": "P U64 U64 P P", "rs_pos": "P P P P U64 P P", "rs_emit": "P U64 U32 U64 P P P P",
-}
-
-
 class CwKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double),
                 ("bytes_alg", C.c_double)]
+
+
+_KINDS = {"P": C.c_void_p, "U64": C.c_uint64, "U32": C.c_uint32, "I": C.c_int, "S": C.c_char_p,
+          "void": None}
+
+
+def _sig(restype, *args):
+    """(restype, argtypes) from kind words (P = a pointer, S = char *, I = int)
+    and struct classes, which stand for a pointer to that struct."""
+    types = []
+    for a in args:
+        types += [_KINDS[k] for k in a.split()] if isinstance(a, str) else [C.POINTER(a)]
+    return _KINDS[restype], types
+
+
+def _batch_call(batch, result, memspace="I"):
+    return _sig("I", "P", batch, result, memspace)
+
+
+# every function include/causeweave.h declares -> (restype, argtypes); the
+# context comes first wherever there is one
+SIGNATURES = {
+    "cw_abi_version": _sig("I"),
+    "cw_build_id": _sig("S"),
+    "cw_ctx_create": _sig("I", "I", C.c_void_p),
+    "cw_ctx_destroy": _sig("void", "P"),
+    "cw_last_error": _sig("S", "P"),
+    "cw_ctx_set_stream": _sig("I", "P P"),
+    "cw_ctx_set_async": _sig("I", "P I"),
+    "cw_ctx_set_profiling": _sig("I", "P I"),
+    "cw_ctx_set_profile_only": _sig("I", "P S"),
+    "cw_ctx_set_option": _sig("I", "P S U32"),
+    "cw_get_kernel_stats": _sig("I", "P", CwKernelStat, "I"),
+    "cw_reset_kernel_stats": _sig("I", "P"),
+    "cw_get_counter": _sig("I", "P S", C.c_uint64),
+    "cw_weave_lists": _batch_call(CwListBatch, CwListResult),
+    "cw_weave_lists_k32": _batch_call(CwListBatchK32, CwListResult),
+    "cw_weave_lists_k128": _batch_call(CwListBatchK128, CwListResult),
+    "cw_weave_maps": _batch_call(CwMapBatch, CwMapResult),
+    "cw_merge_lists": _batch_call(CwMergeBatch, CwMergeResult),
+    "cw_merge_maps": _batch_call(CwMapMergeBatch, CwMapMergeResult),
+    "cw_weft_lists": _batch_call(CwWeftBatch, CwWeftResult),
+    "cw_weft_lists_dev": _batch_call(CwWeftBatch, CwWeftResult, ""),
+    "cw_weft_maps": _batch_call(CwMapWeftBatch, CwMapWeftResult),
+    "cw_render_lists": _batch_call(CwRenderBatch, CwRenderResult),
+    "cw_render_maps": _batch_call(CwMapRenderBatch, CwMapRenderResult),
+    "cw_weave_ranked": _batch_call(CwRankedList, CwListResult, ""),
+    "cw_weave_linked": _batch_call(CwLinkedList, CwListResult, ""),
+    "cw_sort_keys": _sig("I", "P P U64 U32 P P"),
+    "cw_sort_keys32": _sig("I", "P P U64 U32 P P"),
+    "cw_lookup_keys": _sig("I", "P P U64 P U64 U32 P P"),
+    "cw_partition_keys": _sig("I", "P P U64 P U32 P P"),
+    "cw_partition_keys_dev": _sig("I", "P P U64 P U32 P P"),
+    "cw_gather": _sig("I", "P P P U64 U32 P"),
+    "cw_scatter32": _sig("I", "P P P U64 P"),
+    # the distributed tree's building blocks (dist.hip)
+    "cw_dist_check": _sig("I", "P U64 U32 P P P"),
+    "cw_dist_eff": _sig("I", "P U64 U32 P P P"),
+    "cw_dist_climb": _sig("I", "P U64 U32 P P P U64 P"),
+    "cw_dist_pending": _sig("I", "P P U64 P P"),
+    "cw_dist_gkey": _sig("I", "P P P U64 P"),
+    "cw_dist_runs": _sig("I", "P P P U64 U32 P P P P"),
+    "cw_dist_rkey": _sig("I", "P P U64 P"),
+    "cw_dist_link": _sig("I", "P P P U64 P U32 U64 P P P"),
+    "cw_dist_put": _sig("I", "P P P U64 U32 U64 P"),
+    "cw_dist_thr": _sig("I", "P P U64 U32 P"),
+    "cw_dist_succ": _sig("I", "P P P P U64 U32 P"),
+    "cw_dist_rs_rulers": _sig("I", "P P P U64 U32 U32 U32 P P P"),
+    "cw_dist_rs_walk": _sig("I", "P P U64 P U32 P P U64 U32 P P P P P P"),
+    "cw_dist_rs_top": _sig("I", "P P U64 U64 P P"),
+    "cw_dist_rs_pos": _sig("I", "P P P P P U64 P P"),
+    "cw_dist_rs_emit": _sig("I", "P P U64 U32 U64 P P P P"),
+}
 
 
 _LIB = None
@@ -214,78 +272,10 @@ def lib():
                              "'import __graft_entry__ as g; g.build()' or `make`)")
         _share_torch_hip_runtime()
         L = C.CDLL(LIB_PATH)
-        L.cw_abi_version.restype = C.c_int
-        L.cw_build_id.restype = C.c_char_p
-        L.cw_ctx_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
-        L.cw_ctx_create.restype = C.c_int
-        L.cw_ctx_destroy.argtypes = [C.c_void_p]
-        L.cw_ctx_destroy.restype = None
-        L.cw_last_error.argtypes = [C.c_void_p]
-        L.cw_last_error.restype = C.c_char_p
-        L.cw_ctx_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-        L.cw_ctx_set_async.argtypes = [C.c_void_p, C.c_int]
-        L.cw_ctx_set_profiling.argtypes = [C.c_void_p, C.c_int]
-        L.cw_ctx_set_profile_only.argtypes = [C.c_void_p, C.c_char_p]
-        if hasattr(L, "cw_ctx_set_option"):  # (a build from before it, named by CW_LIB for an A/B run)
-            L.cw_ctx_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_uint32]
-        L.cw_get_kernel_stats.argtypes = [C.c_void_p, C.POINTER(CwKernelStat), C.c_int]
-        L.cw_reset_kernel_stats.argtypes = [C.c_void_p]
-        L.cw_get_counter.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64)]
-        L.cw_get_counter.restype = C.c_int
-        L.cw_weave_lists.argtypes = [C.c_void_p, C.POINTER(CwListBatch), C.POINTER(CwListResult),
-                                     C.c_int]
-        L.cw_weave_lists.restype = C.c_int
-        L.cw_weave_lists_k32.argtypes = [C.c_void_p, C.POINTER(CwListBatchK32),
-                                         C.POINTER(CwListResult), C.c_int]
-        L.cw_weave_lists_k32.restype = C.c_int
-        L.cw_weave_lists_k128.argtypes = [C.c_void_p, C.POINTER(CwListBatchK128),
-                                          C.POINTER(CwListResult), C.c_int]
-        L.cw_weave_lists_k128.restype = C.c_int
-        L.cw_weave_maps.argtypes = [C.c_void_p, C.POINTER(CwMapBatch), C.POINTER(CwMapResult),
-                                    C.c_int]
-        L.cw_weave_maps.restype = C.c_int
-        L.cw_merge_lists.argtypes = [C.c_void_p, C.POINTER(CwMergeBatch),
-                                     C.POINTER(CwMergeResult), C.c_int]
-        L.cw_merge_lists.restype = C.c_int
-        L.cw_merge_maps.argtypes = [C.c_void_p, C.POINTER(CwMapMergeBatch),
-                                    C.POINTER(CwMapMergeResult), C.c_int]
-        L.cw_merge_maps.restype = C.c_int
-        L.cw_weft_lists.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch), C.POINTER(CwWeftResult),
-                                    C.c_int]
-        L.cw_weft_lists.restype = C.c_int
-        if hasattr(L, "cw_weft_lists_dev"):  # (a build from before it, named by CW_LIB for an A/B run)
-            L.cw_weft_lists_dev.argtypes = [C.c_void_p, C.POINTER(CwWeftBatch),
-                                            C.POINTER(CwWeftResult)]
-            L.cw_weft_lists_dev.restype = C.c_int
-        if hasattr(L, "cw_weft_maps"):  # (a build from before it, named by CW_LIB for an A/B run)
-            L.cw_weft_maps.argtypes = [C.c_void_p, C.POINTER(CwMapWeftBatch),
-                                       C.POINTER(CwMapWeftResult), C.c_int]
-            L.cw_weft_maps.restype = C.c_int
-        L.cw_render_lists.argtypes = [C.c_void_p, C.POINTER(CwRenderBatch),
-                                      C.POINTER(CwRenderResult), C.c_int]
-        L.cw_render_lists.restype = C.c_int
-        L.cw_render_maps.argtypes = [C.c_void_p, C.POINTER(CwMapRenderBatch),
-                                     C.POINTER(CwMapRenderResult), C.c_int]
-        L.cw_render_maps.restype = C.c_int
-        P, U64, U32 = C.c_void_p, C.c_uint64, C.c_uint32
-        L.cw_sort_keys.argtypes = [P, P, U64, U32, P, P]
-        L.cw_lookup_keys.argtypes = [P, P, U64, P, U64, U32, P, P]
-        L.cw_partition_keys.argtypes = [P, P, U64, P, U32, P, P]
-        L.cw_partition_keys_dev.argtypes = [P, P, U64, P, U32, P, P]
-        L.cw_gather.argtypes = [P, P, P, U64, U32, P]
-        L.cw_scatter32.argtypes = [P, P, P, U64, P]
-        L.cw_weave_ranked.argtypes = [P, C.POINTER(CwRankedList), C.POINTER(CwListResult)]
-        L.cw_weave_linked.argtypes = [P, C.POINTER(CwLinkedList), C.POINTER(CwListResult)]
-        L.cw_sort_keys32.argtypes = [P, P, U64, U32, P, P]
-        L.cw_sort_keys32.restype = C.c_int
-        for f in ("cw_sort_keys", "cw_lookup_keys", "cw_partition_keys", "cw_partition_keys_dev",
-                  "cw_gather", "cw_scatter32",
-                  "cw_weave_ranked", "cw_weave_linked"):
-            getattr(L, f).restype = C.c_int
-        for f, a in _DIST_ARGS.items():
-            fn = getattr(L, "cw_dist_" + f)
-            fn.argtypes = [P] + [{"P": P, "U64": U64, "U32": U32}[x] for x in a.split()]
-            fn.restype = C.c_int
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if hasattr(L, name):  # (an older build, named by CW_LIB for an A/B run, may lack it)
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 
@@ -386,6 +376,78 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
+def _u64p(a):
+    return a.ctypes.data_as(_U64P) if a is not None else None
+
+
+def _vp(p):
+    """A raw device pointer (an int; None or 0 = NULL) as a struct field."""
+    return C.c_void_p(p) if p else None
+
+
+def _u64(a):
+    return np.ascontiguousarray(a, np.uint64)
+
+
+_LIST_DT = (np.uint64, np.uint64, np.uint8)           # id_key, cause_key, kind
+_MAP_DT = (np.uint64, np.uint64, np.uint8, np.uint8)  # id_key, cause, cause_is_id, kind
+
+
+def _host_nodes(offsets, columns, dtypes, what, every=True):
+    """Host offsets and node columns as contiguous arrays of their dtypes.
+    ValueError(what) unless the first column (every: each one) has offsets[-1]
+    elements."""
+    off = _u64(offsets)
+    cols = [np.ascontiguousarray(x, dt) for x, dt in zip(columns, dtypes)]
+    n = int(off[-1])
+    if any(len(x) != n for x in (cols if every else cols[:1])):
+        raise ValueError(what)
+    return off, cols
+
+
+# A ctypes struct keeps no numpy array alive: whoever builds one holds the
+# arrays it points into in locals until the C call has returned.  The builders
+# below return those arrays next to the struct.
+
+def _list_result(out_ptrs, null=()):
+    """CwListResult from a dict of device pointers (absent, None or 0 = NULL)."""
+    return CwListResult(*[None if f in null else _vp(out_ptrs.get(f))
+                          for f, _ in CwListResult._fields_])
+
+
+def _map_result(out_ptrs, cap_segs):
+    """CwMapResult from a dict of device pointers and the key-weave capacity."""
+    return CwMapResult(cap_segs, 0, *[_vp(out_ptrs.get(f)) for f, _ in CwMapResult._fields_[2:]])
+
+
+def _new_list_result(n, words, D, yarns):
+    """Zeroed host arrays of a list result (n per node, `words` of bitmap, D
+    per document) and the CwListResult that points at them."""
+    out = ListResult(np.zeros(n, np.uint32), np.zeros(words, np.uint32), np.zeros(D, np.uint32),
+                     np.zeros(D, np.uint64), np.zeros(D, np.uint32),
+                     np.zeros(n, np.uint32) if yarns else None)
+    return out, CwListResult(*[_ptr(getattr(out, f)) for f, _ in CwListResult._fields_])
+
+
+def _trim_list_result(w, M, D):
+    return ListResult(w.weave_perm[:M], w.visible_bits[:(M + 31) // 32], w.visible_count[:D],
+                      w.max_ts[:D], w.status[:D], None if w.yarn_perm is None else w.yarn_perm[:M])
+
+
+def _new_map_result(cap, nodes, D):
+    """Zeroed host arrays of a map result (cap key weaves over `nodes` nodes in
+    D collections) and the CwMapResult that points at them."""
+    out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
+                    np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
+                    np.zeros(nodes + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
+    return out, CwMapResult(cap, 0, *[_ptr(getattr(out, f)) for f, _ in CwMapResult._fields_[2:]])
+
+
+def _trim_map_result(out, S, M, D):
+    return MapResult(out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S],
+                     out.seg_active[:S], out.seg_perm[:M + S], out.status[:D])
+
+
 class Weaver:
     """A weave context on one HIP device (cw_ctx)."""
 
@@ -457,134 +519,77 @@ class Weaver:
         return int(v.value)
 
     @staticmethod
-    def _batch(offsets, id_ptr, cause_ptr, kind_ptr, layout, key_bits=None):
-        off = np.ascontiguousarray(offsets, np.uint64)
-        b = CwListBatch()
-        b.n_docs = len(off) - 1
-        b.doc_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause_key, b.kind = id_ptr, cause_ptr, kind_ptr
-        b.key_bits = layout.key_bits if key_bits is None else key_bits
-        b.ts_shift = layout.ts_shift
-        b.site_shift = layout.site_shift
-        b.site_bits = layout.site_bits
+    def _list_batch(cls, offsets, id_ptr, cause_ptr, kind_ptr, layout=None, key_bits=None, **more):
+        """A CwListBatch / K32 / K128 and the offsets array it points into."""
+        off = _u64(offsets)
+        b = cls(len(off) - 1, _u64p(off), id_ptr, cause_ptr, kind_ptr, **more)
+        if layout is not None:
+            b.key_bits = layout.key_bits if key_bits is None else key_bits
+            b.ts_shift, b.site_shift, b.site_bits = layout.ts_shift, layout.site_shift, layout.site_bits
         return b, off
+
+    @staticmethod
+    def _batch(offsets, id_ptr, cause_ptr, kind_ptr, layout, key_bits=None):
+        return Weaver._list_batch(CwListBatch, offsets, id_ptr, cause_ptr, kind_ptr, layout, key_bits)
+
+    def _weave_host(self, fn, b, N, D, yarns) -> ListResult:
+        out, r = _new_list_result(N, (N + 31) // 32, D, yarns)
+        self._check(getattr(self._L, fn)(self._h, C.byref(b), C.byref(r), CW_MEM_HOST), fn)
+        return out
+
+    def _weave_device(self, fn, b, out_ptrs):
+        r = _list_result(out_ptrs)
+        self._check(getattr(self._L, fn)(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE), fn)
 
     def weave_lists(self, offsets, id_key, cause_key, kind, layout, yarns=True,
                     key_bits=None) -> ListResult:
         """Host-memory call: numpy in, numpy out."""
-        i = np.ascontiguousarray(id_key, np.uint64)
-        c = np.ascontiguousarray(cause_key, np.uint64)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        D, N = len(off) - 1, len(i)
-        if int(off[-1]) != N:
-            raise ValueError("offsets[-1] != number of nodes")
-        b, off = self._batch(off, _ptr(i), _ptr(c), _ptr(k), layout, key_bits)
-        out = ListResult(np.zeros(N, np.uint32), np.zeros((N + 31) // 32, np.uint32),
-                         np.zeros(D, np.uint32), np.zeros(D, np.uint64), np.zeros(D, np.uint32),
-                         np.zeros(N, np.uint32) if (yarns and layout.site_bits) else None)
-        r = CwListResult(_ptr(out.weave_perm), _ptr(out.visible_bits), _ptr(out.visible_count),
-                         _ptr(out.max_ts), _ptr(out.status), _ptr(out.yarn_perm))
-        self._check(self._L.cw_weave_lists(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
-                    "cw_weave_lists")
-        return out
+        off, cols = _host_nodes(offsets, (id_key, cause_key, kind), _LIST_DT,
+                                "offsets[-1] != number of nodes", every=False)
+        b, off = self._batch(off, *map(_ptr, cols), layout, key_bits)
+        return self._weave_host("cw_weave_lists", b, len(cols[0]), len(off) - 1,
+                                yarns and layout.site_bits)
 
     def weave_lists_device(self, offsets, id_ptr, cause_ptr, kind_ptr, layout, out_ptrs,
                            key_bits=None):
         """Device-memory call: raw device pointers (e.g. torch tensor data_ptr()).
         out_ptrs: dict with weave_perm, visible_bits, visible_count, max_ts,
         status, yarn_perm (None allowed where the header allows NULL)."""
-        b, off = self._batch(offsets, C.c_void_p(id_ptr), C.c_void_p(cause_ptr),
-                             C.c_void_p(kind_ptr), layout, key_bits)
-        g = lambda n: C.c_void_p(out_ptrs[n]) if out_ptrs.get(n) else None
-        r = CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"), g("max_ts"),
-                         g("status"), g("yarn_perm"))
-        self._check(self._L.cw_weave_lists(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
-                    "cw_weave_lists")
+        b, off = self._batch(offsets, _vp(id_ptr), _vp(cause_ptr), _vp(kind_ptr), layout, key_bits)
+        self._weave_device("cw_weave_lists", b, out_ptrs)
 
     def weave_lists_k32(self, offsets, id_key, cause_key, kind, layout, yarns=True,
                         key_bits=None) -> ListResult:
         """Host-memory call of cw_weave_lists_k32: id_key / cause_key are uint32
         (nil = NIL32, see narrow_k32)."""
-        i = np.ascontiguousarray(id_key, np.uint32)
-        c = np.ascontiguousarray(cause_key, np.uint32)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        D, N = len(off) - 1, len(i)
-        if int(off[-1]) != N or len(c) != N or len(k) != N:
-            raise ValueError("offsets[-1] / id_key / cause_key / kind sizes differ")
-        b, off = self._batch_k32(off, _ptr(i), _ptr(c), _ptr(k), layout, key_bits)
-        out = ListResult(np.zeros(N, np.uint32), np.zeros((N + 31) // 32, np.uint32),
-                         np.zeros(D, np.uint32), np.zeros(D, np.uint64), np.zeros(D, np.uint32),
-                         np.zeros(N, np.uint32) if (yarns and layout.site_bits) else None)
-        r = CwListResult(_ptr(out.weave_perm), _ptr(out.visible_bits), _ptr(out.visible_count),
-                         _ptr(out.max_ts), _ptr(out.status), _ptr(out.yarn_perm))
-        self._check(self._L.cw_weave_lists_k32(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
-                    "cw_weave_lists_k32")
-        return out
-
-    @staticmethod
-    def _batch_k32(offsets, id_ptr, cause_ptr, kind_ptr, layout, key_bits=None, perm16=False):
-        off = np.ascontiguousarray(offsets, np.uint64)
-        b = CwListBatchK32()
-        b.n_docs = len(off) - 1
-        b.doc_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause_key, b.kind = id_ptr, cause_ptr, kind_ptr
-        b.key_bits = layout.key_bits if key_bits is None else key_bits
-        b.ts_shift, b.site_shift, b.site_bits = layout.ts_shift, layout.site_shift, layout.site_bits
-        b.perm16 = int(perm16)
-        return b, off
+        off, cols = _host_nodes(offsets, (id_key, cause_key, kind), (np.uint32, np.uint32, np.uint8),
+                                "offsets[-1] / id_key / cause_key / kind sizes differ")
+        b, off = self._list_batch(CwListBatchK32, off, *map(_ptr, cols), layout, key_bits, perm16=0)
+        return self._weave_host("cw_weave_lists_k32", b, len(cols[0]), len(off) - 1,
+                                yarns and layout.site_bits)
 
     def weave_lists_k32_device(self, offsets, id_ptr, cause_ptr, kind_ptr, layout, out_ptrs,
                                key_bits=None, perm16=False):
         """Device-memory call of cw_weave_lists_k32 (u32 keys; out_ptrs as
         weave_lists_device; perm16: weave_perm is uint16 per node)."""
-        b, off = self._batch_k32(offsets, C.c_void_p(id_ptr), C.c_void_p(cause_ptr),
-                                 C.c_void_p(kind_ptr), layout, key_bits, perm16)
-        g = lambda n: C.c_void_p(out_ptrs[n]) if out_ptrs.get(n) else None
-        r = CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"), g("max_ts"),
-                         g("status"), g("yarn_perm"))
-        self._check(self._L.cw_weave_lists_k32(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
-                    "cw_weave_lists_k32")
-
-    @staticmethod
-    def _batch_k128(offsets, id_ptr, cause_ptr, kind_ptr):
-        off = np.ascontiguousarray(offsets, np.uint64)
-        b = CwListBatchK128()
-        b.n_docs = len(off) - 1
-        b.doc_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause_key, b.kind = id_ptr, cause_ptr, kind_ptr
-        return b, off
+        b, off = self._list_batch(CwListBatchK32, offsets, _vp(id_ptr), _vp(cause_ptr),
+                                  _vp(kind_ptr), layout, key_bits, perm16=int(perm16))
+        self._weave_device("cw_weave_lists_k32", b, out_ptrs)
 
     def weave_lists_k128(self, offsets, id_key, cause_key, kind, yarns=True) -> ListResult:
         """Host-memory call of cw_weave_lists_k128: id_key / cause_key are
         uint64[N, 2] (hi = ts, lo = site_rank << 32 | tx; nil = (NIL, NIL))."""
-        i = np.ascontiguousarray(id_key, np.uint64).reshape(-1, 2)
-        c = np.ascontiguousarray(cause_key, np.uint64).reshape(-1, 2)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        D, N = len(off) - 1, len(k)
-        if int(off[-1]) != N or len(i) != N or len(c) != N:
-            raise ValueError("offsets[-1] / id_key / cause_key / kind sizes differ")
-        b, off = self._batch_k128(off, _ptr(i), _ptr(c), _ptr(k))
-        out = ListResult(np.zeros(N, np.uint32), np.zeros((N + 31) // 32, np.uint32),
-                         np.zeros(D, np.uint32), np.zeros(D, np.uint64), np.zeros(D, np.uint32),
-                         np.zeros(N, np.uint32) if yarns else None)
-        r = CwListResult(_ptr(out.weave_perm), _ptr(out.visible_bits), _ptr(out.visible_count),
-                         _ptr(out.max_ts), _ptr(out.status), _ptr(out.yarn_perm))
-        self._check(self._L.cw_weave_lists_k128(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
-                    "cw_weave_lists_k128")
-        return out
+        i, c = (_u64(x).reshape(-1, 2) for x in (id_key, cause_key))
+        off, cols = _host_nodes(offsets, (i, c, kind), _LIST_DT,
+                                "offsets[-1] / id_key / cause_key / kind sizes differ")
+        b, off = self._list_batch(CwListBatchK128, off, *map(_ptr, cols))
+        return self._weave_host("cw_weave_lists_k128", b, len(cols[2]), len(off) - 1, yarns)
 
     def weave_lists_k128_device(self, offsets, id_ptr, cause_ptr, kind_ptr, out_ptrs):
         """Device-memory call of cw_weave_lists_k128 (out_ptrs as weave_lists_device)."""
-        b, off = self._batch_k128(offsets, C.c_void_p(id_ptr), C.c_void_p(cause_ptr),
-                                  C.c_void_p(kind_ptr))
-        g = lambda n: C.c_void_p(out_ptrs[n]) if out_ptrs.get(n) else None
-        r = CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"), g("max_ts"),
-                         g("status"), g("yarn_perm"))
-        self._check(self._L.cw_weave_lists_k128(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
-                    "cw_weave_lists_k128")
+        b, off = self._list_batch(CwListBatchK128, offsets, _vp(id_ptr), _vp(cause_ptr),
+                                  _vp(kind_ptr))
+        self._weave_device("cw_weave_lists_k128", b, out_ptrs)
 
     # --- building blocks of the distributed giant list (device pointers) ---------
     def sort_keys_device(self, keys_ptr, n, key_bits, keys_out_ptr, idx_out_ptr):
@@ -632,9 +637,7 @@ class Weaver:
     def weave_ranked_device(self, n, par_ptr, kind_ptr, val_ptr, out_ptrs):
         """out_ptrs: weave_perm, visible_bits (or None), visible_count, status."""
         lst = CwRankedList(n, par_ptr, kind_ptr, val_ptr)
-        g = lambda k: C.c_void_p(out_ptrs[k]) if out_ptrs.get(k) else None
-        r = CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"), None, g("status"),
-                         None)
+        r = _list_result(out_ptrs, null=("max_ts", "yarn_perm"))
         self._check(self._L.cw_weave_ranked(self._h, C.byref(lst), C.byref(r)), "cw_weave_ranked")
 
     def sort_keys32_device(self, keys_ptr, n, key_bits, keys_out_ptr, idx_out_ptr):
@@ -649,100 +652,85 @@ class Weaver:
     def weave_linked_device(self, n, succ_ptr, thr_ptr, val_ptr, out_ptrs):
         """cw_weave_linked: out_ptrs as weave_ranked_device."""
         lst = CwLinkedList(n, succ_ptr, thr_ptr, val_ptr)
-        g = lambda k: C.c_void_p(out_ptrs[k]) if out_ptrs.get(k) else None
-        r = CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"), None, g("status"),
-                         None)
+        r = _list_result(out_ptrs, null=("max_ts", "yarn_perm"))
         self._check(self._L.cw_weave_linked(self._h, C.byref(lst), C.byref(r)), "cw_weave_linked")
+
+    # --- merge and weft: a node selection per document, then its weave --------------
+    def _kept_lists_host(self, fn, batch, result, nodes, words, D, yarns) -> MergeResult:
+        """The host call of a list merge or weft: room for `nodes` in every
+        per-node array, the result trimmed to the offsets the library returns."""
+        offs, src = np.zeros(D + 1, np.uint64), np.zeros(nodes, np.uint32)
+        w, wr = _new_list_result(nodes, words, max(D, 1), yarns)
+        r = result(_u64p(offs), _ptr(src), wr)
+        self._check(getattr(self._L, fn)(self._h, C.byref(batch), C.byref(r), CW_MEM_HOST), fn)
+        M = int(offs[-1])
+        return MergeResult(offs, src[:M], _trim_list_result(w, M, D))
+
+    def _kept_lists_device(self, fn, batch, result, D, src_ptr, out_ptrs, *memspace):
+        offs = np.zeros(D + 1, np.uint64)
+        r = result(_u64p(offs), _vp(src_ptr), _list_result(out_ptrs))
+        self._check(getattr(self._L, fn)(self._h, C.byref(batch), C.byref(r), *memspace), fn)
+        return offs
+
+    def _kept_maps_host(self, fn, batch, result, nodes, D):
+        """As _kept_lists_host for maps: (offsets, src, MapResult), every node a
+        possible key weave."""
+        cap = max(nodes, 1)
+        offs, src = np.zeros(D + 1, np.uint64), np.zeros(cap, np.uint32)
+        out, mr = _new_map_result(cap, nodes, D)
+        r = result(_u64p(offs), _ptr(src), mr)
+        self._check(getattr(self._L, fn)(self._h, C.byref(batch), C.byref(r), CW_MEM_HOST), fn)
+        S, M = int(r.maps.n_segs), int(offs[-1])
+        return offs, src[:M], _trim_map_result(out, S, M, D)
+
+    def _kept_maps_device(self, fn, batch, result, D, src_ptr, out_ptrs, cap_segs):
+        offs = np.zeros(D + 1, np.uint64)
+        r = result(_u64p(offs), _vp(src_ptr), _map_result(out_ptrs, cap_segs))
+        self._check(getattr(self._L, fn)(self._h, C.byref(batch), C.byref(r), CW_MEM_DEVICE), fn)
+        return offs, int(r.maps.n_segs)
 
     def merge_lists(self, a, b, layout, yarns=True) -> MergeResult:
         """Host-memory call of cw_merge_lists.  a, b: (offsets, id_key, cause_key,
         kind, value_token) per side, with the same number of documents."""
-        def side(t):
-            off, i, c, k, v = t
-            off = np.ascontiguousarray(off, np.uint64)
-            arrs = (np.ascontiguousarray(i, np.uint64), np.ascontiguousarray(c, np.uint64),
-                    np.ascontiguousarray(k, np.uint8), np.ascontiguousarray(v, np.uint64))
-            if int(off[-1]) != len(arrs[0]):
-                raise ValueError("offsets[-1] != number of nodes")
-            return off, arrs
-        ao, (ai, ac, ak, av) = side(a)
-        bo, (bi, bc, bk, bv) = side(b)
+        what = "offsets[-1] != number of nodes"
+        ao, ac = _host_nodes(a[0], a[1:], _LIST_DT + (np.uint64,), what, every=False)
+        bo, bc = _host_nodes(b[0], b[1:], _LIST_DT + (np.uint64,), what, every=False)
         if len(ao) != len(bo):
             raise ValueError("a and b must have the same number of documents")
-        D, NC = len(ao) - 1, len(ai) + len(bi)
-        ba, _ = self._batch(ao, _ptr(ai), _ptr(ac), _ptr(ak), layout)
-        bb, _ = self._batch(bo, _ptr(bi), _ptr(bc), _ptr(bk), layout)
-        mb = CwMergeBatch(ba, _ptr(av), bb, _ptr(bv))
-        mo = np.zeros(D + 1, np.uint64)
-        src = np.zeros(max(NC, 1), np.uint32)
-        w = ListResult(np.zeros(max(NC, 1), np.uint32), np.zeros((NC + 31) // 32 + 1, np.uint32),
-                       np.zeros(max(D, 1), np.uint32), np.zeros(max(D, 1), np.uint64),
-                       np.zeros(max(D, 1), np.uint32),
-                       np.zeros(max(NC, 1), np.uint32) if (yarns and layout.site_bits) else None)
-        r = CwMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
-                          CwListResult(_ptr(w.weave_perm), _ptr(w.visible_bits),
-                                       _ptr(w.visible_count), _ptr(w.max_ts), _ptr(w.status),
-                                       _ptr(w.yarn_perm)))
-        self._check(self._L.cw_merge_lists(self._h, C.byref(mb), C.byref(r), CW_MEM_HOST),
-                    "cw_merge_lists")
-        M = int(mo[-1])
-        w = ListResult(w.weave_perm[:M], w.visible_bits[:(M + 31) // 32], w.visible_count[:D],
-                       w.max_ts[:D], w.status[:D], None if w.yarn_perm is None else w.yarn_perm[:M])
-        return MergeResult(mo, src[:M], w)
+        D, NC = len(ao) - 1, len(ac[0]) + len(bc[0])
+        # (ao and bo are uint64 arrays already, so the batches point into them)
+        mb = CwMergeBatch(self._batch(ao, *map(_ptr, ac[:3]), layout)[0], _ptr(ac[3]),
+                          self._batch(bo, *map(_ptr, bc[:3]), layout)[0], _ptr(bc[3]))
+        return self._kept_lists_host("cw_merge_lists", mb, CwMergeResult, max(NC, 1),
+                                     (NC + 31) // 32 + 1, D, yarns and layout.site_bits)
 
     def merge_lists_device(self, a_offsets, a_ptrs, b_offsets, b_ptrs, layout, src_ptr, out_ptrs):
         """Device-memory call of cw_merge_lists.  a_ptrs / b_ptrs = (id_key,
         cause_key, kind, value) device pointers; src_ptr: merged_src (uint32
         [Na+Nb]); out_ptrs as weave_lists_device, every array sized for Na+Nb.
         Returns the merged offsets (uint64[D+1])."""
-        ao = np.ascontiguousarray(a_offsets, np.uint64)
-        bo = np.ascontiguousarray(b_offsets, np.uint64)
+        ao, bo = _u64(a_offsets), _u64(b_offsets)
         if len(ao) != len(bo):
             raise ValueError("a and b must have the same number of documents")
-        vp = lambda p: C.c_void_p(p) if p else None
-        ba, _ = self._batch(ao, vp(a_ptrs[0]), vp(a_ptrs[1]), vp(a_ptrs[2]), layout)
-        bb, _ = self._batch(bo, vp(b_ptrs[0]), vp(b_ptrs[1]), vp(b_ptrs[2]), layout)
-        mb = CwMergeBatch(ba, vp(a_ptrs[3]), bb, vp(b_ptrs[3]))
-        mo = np.zeros(len(ao), np.uint64)
-        g = lambda n: vp(out_ptrs.get(n))
-        r = CwMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
-                          CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"),
-                                       g("max_ts"), g("status"), g("yarn_perm")))
-        self._check(self._L.cw_merge_lists(self._h, C.byref(mb), C.byref(r), CW_MEM_DEVICE),
-                    "cw_merge_lists")
-        return mo
+        mb = CwMergeBatch(self._batch(ao, *map(_vp, a_ptrs[:3]), layout)[0], _vp(a_ptrs[3]),
+                          self._batch(bo, *map(_vp, b_ptrs[:3]), layout)[0], _vp(b_ptrs[3]))
+        return self._kept_lists_device("cw_merge_lists", mb, CwMergeResult, len(ao) - 1, src_ptr,
+                                       out_ptrs, CW_MEM_DEVICE)
 
     def weft_lists(self, offsets, id_key, cause_key, kind, layout, cut, yarns=True) -> MergeResult:
         """Host-memory call of cw_weft_lists.  cut: uint64[D << site_bits] packed
         cut id per (document, site rank), 0 = site not named.  Returns the kept
         nodes (src = doc-local input index, input order) and their weave."""
-        i = np.ascontiguousarray(id_key, np.uint64)
-        c = np.ascontiguousarray(cause_key, np.uint64)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        cut = np.ascontiguousarray(cut, np.uint64)
-        D, N = len(off) - 1, len(i)
-        if int(off[-1]) != N or len(cut) != D << layout.site_bits:
+        cut = _u64(cut)
+        off, cols = _host_nodes(offsets, (id_key, cause_key, kind), _LIST_DT,
+                                "offsets / cut sizes", every=False)
+        D, N = len(off) - 1, len(cols[0])
+        if len(cut) != D << layout.site_bits:
             raise ValueError("offsets / cut sizes")
-        b, off = self._batch(off, _ptr(i), _ptr(c), _ptr(k), layout)
-        wb = CwWeftBatch(b, cut.ctypes.data_as(C.POINTER(C.c_uint64)))
-        ko = np.zeros(D + 1, np.uint64)
+        b, off = self._batch(off, *map(_ptr, cols), layout)
         cap = max(N + (D << layout.site_bits), 1)  # + one [id] node per named site
-        src = np.zeros(cap, np.uint32)
-        w = ListResult(np.zeros(cap, np.uint32), np.zeros((cap + 31) // 32 + 1, np.uint32),
-                       np.zeros(max(D, 1), np.uint32), np.zeros(max(D, 1), np.uint64),
-                       np.zeros(max(D, 1), np.uint32),
-                       np.zeros(cap, np.uint32) if (yarns and layout.site_bits) else None)
-        r = CwWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
-                         CwListResult(_ptr(w.weave_perm), _ptr(w.visible_bits),
-                                      _ptr(w.visible_count), _ptr(w.max_ts), _ptr(w.status),
-                                      _ptr(w.yarn_perm)))
-        self._check(self._L.cw_weft_lists(self._h, C.byref(wb), C.byref(r), CW_MEM_HOST),
-                    "cw_weft_lists")
-        M = int(ko[-1])
-        w = ListResult(w.weave_perm[:M], w.visible_bits[:(M + 31) // 32], w.visible_count[:D],
-                       w.max_ts[:D], w.status[:D], None if w.yarn_perm is None else w.yarn_perm[:M])
-        return MergeResult(ko, src[:M], w)
+        return self._kept_lists_host("cw_weft_lists", CwWeftBatch(b, _u64p(cut)), CwWeftResult,
+                                     cap, (cap + 31) // 32 + 1, D, yarns and layout.site_bits)
 
     def weft_lists_device(self, offsets, ptrs, layout, cut_ptr, src_ptr, out_ptrs):
         """Device-memory call (cw_weft_lists_dev).  ptrs = (id_key, cause_key,
@@ -750,32 +738,26 @@ class Weaver:
         src_ptr: kept_src (uint32); out_ptrs as weave_lists_device; src and
         every per-node array sized for N + (D << site_bits).  Returns the kept
         offsets (uint64[D+1])."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        b, off = self._batch(offsets, vp(ptrs[0]), vp(ptrs[1]), vp(ptrs[2]), layout)
-        wb = CwWeftBatch(b, C.cast(vp(cut_ptr), C.POINTER(C.c_uint64)))
-        ko = np.zeros(len(off), np.uint64)
-        g = lambda n: vp(out_ptrs.get(n))
-        r = CwWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
-                         CwListResult(g("weave_perm"), g("visible_bits"), g("visible_count"),
-                                      g("max_ts"), g("status"), g("yarn_perm")))
-        self._check(self._L.cw_weft_lists_dev(self._h, C.byref(wb), C.byref(r)),
-                    "cw_weft_lists_dev")
-        return ko
+        b, off = self._batch(offsets, *map(_vp, ptrs[:3]), layout)
+        wb = CwWeftBatch(b, C.cast(_vp(cut_ptr), _U64P))
+        return self._kept_lists_device("cw_weft_lists_dev", wb, CwWeftResult, len(off) - 1,
+                                       src_ptr, out_ptrs)
+
+    # --- maps ---------------------------------------------------------------------
+    @staticmethod
+    def _map_batch(off, ptrs, key_bits, token_bits):
+        """A CwMapBatch over `off`, a uint64 array the caller keeps alive."""
+        b = CwMapBatch(len(off) - 1, _u64p(off), key_bits=key_bits, token_bits=token_bits)
+        b.id_key, b.cause, b.cause_is_id, b.kind = ptrs
+        return b
 
     def weave_maps_device(self, offsets, ptrs, token_bits, key_bits, out_ptrs, cap_segs) -> int:
         """Device-memory call of cw_weave_maps: ptrs = (id_key, cause, cause_is_id,
         kind) device pointers; out_ptrs: seg_offsets, seg_coll, seg_key,
         seg_active, seg_perm, status device pointers.  Returns n_segs."""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        b = CwMapBatch()
-        b.n_colls = len(off) - 1
-        b.coll_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause, b.cause_is_id, b.kind = (C.c_void_p(p) for p in ptrs)
-        b.key_bits = key_bits
-        b.token_bits = token_bits
-        g = lambda n: C.c_void_p(out_ptrs[n])
-        r = CwMapResult(cap_segs, 0, g("seg_offsets"), g("seg_coll"), g("seg_key"),
-                        g("seg_active"), g("seg_perm"), g("status"))
+        off = _u64(offsets)
+        b = self._map_batch(off, [_vp(p) for p in ptrs], key_bits, token_bits)
+        r = _map_result(out_ptrs, cap_segs)
         self._check(self._L.cw_weave_maps(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
                     "cw_weave_maps")
         return int(r.n_segs)
@@ -783,41 +765,14 @@ class Weaver:
     def weave_maps(self, offsets, id_key, cause, cause_is_id, kind, token_bits,
                    key_bits=0) -> MapResult:
         """Host-memory call of cw_weave_maps."""
-        i = np.ascontiguousarray(id_key, np.uint64)
-        c = np.ascontiguousarray(cause, np.uint64)
-        ci = np.ascontiguousarray(cause_is_id, np.uint8)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        D, N = len(off) - 1, len(i)
-        if int(off[-1]) != N:
-            raise ValueError("offsets[-1] != number of nodes")
-        b = CwMapBatch()
-        b.n_colls = D
-        b.coll_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause, b.cause_is_id, b.kind = _ptr(i), _ptr(c), _ptr(ci), _ptr(k)
-        b.key_bits = key_bits
-        b.token_bits = token_bits
-        cap = max(N, 1)
-        out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
-                        np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
-                        np.zeros(N + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
-        r = CwMapResult(cap, 0, _ptr(out.seg_offsets), _ptr(out.seg_coll), _ptr(out.seg_key),
-                        _ptr(out.seg_active), _ptr(out.seg_perm), _ptr(out.status))
+        off, cols = _host_nodes(offsets, (id_key, cause, cause_is_id, kind), _MAP_DT,
+                                "offsets[-1] != number of nodes", every=False)
+        D, N = len(off) - 1, len(cols[0])
+        b = self._map_batch(off, [_ptr(x) for x in cols], key_bits, token_bits)
+        out, r = _new_map_result(max(N, 1), N, D)
         self._check(self._L.cw_weave_maps(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
                     "cw_weave_maps")
-        S = int(r.n_segs)
-        return MapResult(out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S],
-                         out.seg_active[:S], out.seg_perm[:N + S], out.status[:D])
-
-    @staticmethod
-    def _map_batch(off, ptrs, key_bits, token_bits):
-        b = CwMapBatch()
-        b.n_colls = len(off) - 1
-        b.coll_offsets = off.ctypes.data_as(C.POINTER(C.c_uint64))
-        b.id_key, b.cause, b.cause_is_id, b.kind = ptrs
-        b.key_bits = key_bits
-        b.token_bits = token_bits
-        return b
+        return _trim_map_result(out, int(r.n_segs), N, D)
 
     def merge_maps_device(self, a_offsets, a_ptrs, b_offsets, b_ptrs, token_bits, key_bits,
                           src_ptr, out_ptrs, cap_segs):
@@ -825,61 +780,29 @@ class Weaver:
         cause_is_id, kind, value) device pointers; src_ptr: merged_src (uint32
         [Na+Nb]); out_ptrs as weave_maps_device (seg_perm sized Na+Nb+cap_segs).
         Returns (merged offsets uint64[D+1], n_segs)."""
-        ao = np.ascontiguousarray(a_offsets, np.uint64)
-        bo = np.ascontiguousarray(b_offsets, np.uint64)
+        ao, bo = _u64(a_offsets), _u64(b_offsets)
         if len(ao) != len(bo):
             raise ValueError("a and b must have the same number of collections")
-        vp = lambda p: C.c_void_p(p) if p else None
-        ba = self._map_batch(ao, [vp(p) for p in a_ptrs[:4]], key_bits, token_bits)
-        bb = self._map_batch(bo, [vp(p) for p in b_ptrs[:4]], key_bits, token_bits)
-        mb = CwMapMergeBatch(ba, vp(a_ptrs[4]), bb, vp(b_ptrs[4]))
-        mo = np.zeros(len(ao), np.uint64)
-        g = lambda n: C.c_void_p(out_ptrs[n])
-        r = CwMapMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
-                             CwMapResult(cap_segs, 0, g("seg_offsets"), g("seg_coll"),
-                                         g("seg_key"), g("seg_active"), g("seg_perm"),
-                                         g("status")))
-        self._check(self._L.cw_merge_maps(self._h, C.byref(mb), C.byref(r), CW_MEM_DEVICE),
-                    "cw_merge_maps")
-        return mo, int(r.maps.n_segs)
+        ba = self._map_batch(ao, [_vp(p) for p in a_ptrs[:4]], key_bits, token_bits)
+        bb = self._map_batch(bo, [_vp(p) for p in b_ptrs[:4]], key_bits, token_bits)
+        mb = CwMapMergeBatch(ba, _vp(a_ptrs[4]), bb, _vp(b_ptrs[4]))
+        return self._kept_maps_device("cw_merge_maps", mb, CwMapMergeResult, len(ao) - 1, src_ptr,
+                                      out_ptrs, cap_segs)
 
     def merge_maps(self, a, b, token_bits, key_bits=0) -> MapMergeResult:
         """Host-memory call of cw_merge_maps.  a, b: (offsets, id_key, cause,
         cause_is_id, kind, value_token) per side, with the same number of
         collections."""
-        def side(t):
-            off, i, c, ci, k, v = t
-            off = np.ascontiguousarray(off, np.uint64)
-            arrs = (np.ascontiguousarray(i, np.uint64), np.ascontiguousarray(c, np.uint64),
-                    np.ascontiguousarray(ci, np.uint8), np.ascontiguousarray(k, np.uint8),
-                    np.ascontiguousarray(v, np.uint64))
-            if int(off[-1]) != len(arrs[0]) or len({len(x) for x in arrs}) != 1:
-                raise ValueError("offsets[-1] != number of nodes")
-            return off, arrs
-        ao, aa = side(a)
-        bo, ab = side(b)
+        what = "offsets[-1] != number of nodes"
+        ao, aa = _host_nodes(a[0], a[1:], _MAP_DT + (np.uint64,), what)
+        bo, ab = _host_nodes(b[0], b[1:], _MAP_DT + (np.uint64,), what)
         if len(ao) != len(bo):
             raise ValueError("a and b must have the same number of collections")
-        D, NC = len(ao) - 1, len(aa[0]) + len(ab[0])
         ba = self._map_batch(ao, [_ptr(x) for x in aa[:4]], key_bits, token_bits)
         bb = self._map_batch(bo, [_ptr(x) for x in ab[:4]], key_bits, token_bits)
         mb = CwMapMergeBatch(ba, _ptr(aa[4]), bb, _ptr(ab[4]))
-        mo = np.zeros(D + 1, np.uint64)
-        src = np.zeros(max(NC, 1), np.uint32)
-        cap = max(NC, 1)
-        out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
-                        np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
-                        np.zeros(NC + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
-        r = CwMapMergeResult(mo.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
-                             CwMapResult(cap, 0, _ptr(out.seg_offsets), _ptr(out.seg_coll),
-                                         _ptr(out.seg_key), _ptr(out.seg_active),
-                                         _ptr(out.seg_perm), _ptr(out.status)))
-        self._check(self._L.cw_merge_maps(self._h, C.byref(mb), C.byref(r), CW_MEM_HOST),
-                    "cw_merge_maps")
-        S, M = int(r.maps.n_segs), int(mo[-1])
-        return MapMergeResult(mo, src[:M], MapResult(
-            out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
-            out.seg_perm[:M + S], out.status[:D]))
+        return MapMergeResult(*self._kept_maps_host("cw_merge_maps", mb, CwMapMergeResult,
+                                                    len(aa[0]) + len(ab[0]), len(ao) - 1))
 
     def weft_maps_device(self, offsets, ptrs, token_bits, key_bits, site_shift, site_bits, cut_ptr,
                          src_ptr, out_ptrs, cap_segs):
@@ -888,18 +811,11 @@ class Weaver:
         device memory; src_ptr: kept_src (uint32[N + (D << site_bits)]); out_ptrs
         as weave_maps_device (seg_perm sized N + (D << site_bits) + cap_segs).
         Returns (kept offsets uint64[D+1], n_segs)."""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        vp = lambda p: C.c_void_p(p) if p else None
-        wb = CwMapWeftBatch(self._map_batch(off, [vp(p) for p in ptrs], key_bits, token_bits),
-                            site_shift, site_bits, vp(cut_ptr))
-        ko = np.zeros(len(off), np.uint64)
-        g = lambda n: C.c_void_p(out_ptrs[n])
-        r = CwMapWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr),
-                            CwMapResult(cap_segs, 0, g("seg_offsets"), g("seg_coll"), g("seg_key"),
-                                        g("seg_active"), g("seg_perm"), g("status")))
-        self._check(self._L.cw_weft_maps(self._h, C.byref(wb), C.byref(r), CW_MEM_DEVICE),
-                    "cw_weft_maps")
-        return ko, int(r.maps.n_segs)
+        off = _u64(offsets)
+        wb = CwMapWeftBatch(self._map_batch(off, [_vp(p) for p in ptrs], key_bits, token_bits),
+                            site_shift, site_bits, _vp(cut_ptr))
+        return self._kept_maps_device("cw_weft_maps", wb, CwMapWeftResult, len(off) - 1, src_ptr,
+                                      out_ptrs, cap_segs)
 
     def weft_maps(self, offsets, id_key, cause, cause_is_id, kind, token_bits, site_shift,
                   site_bits, cut, key_bits=0) -> MapWeftResult:
@@ -907,36 +823,17 @@ class Weaver:
         cut id per (collection, site rank), 0 = site not named.  Returns the kept
         nodes (src = collection-local input index, input order, then UINT32_MAX
         per [id] node) and their map weave."""
-        i = np.ascontiguousarray(id_key, np.uint64)
-        c = np.ascontiguousarray(cause, np.uint64)
-        ci = np.ascontiguousarray(cause_is_id, np.uint8)
-        k = np.ascontiguousarray(kind, np.uint8)
-        off = np.ascontiguousarray(offsets, np.uint64)
-        cut = np.ascontiguousarray(cut, np.uint64)
-        D, N = len(off) - 1, len(i)
-        if int(off[-1]) != N or len({len(x) for x in (i, c, ci, k)}) != 1:
-            raise ValueError("offsets[-1] != number of nodes")
+        cut = _u64(cut)
+        off, cols = _host_nodes(offsets, (id_key, cause, cause_is_id, kind), _MAP_DT,
+                                "offsets[-1] != number of nodes")
+        D, N = len(off) - 1, len(cols[0])
         if 1 <= site_bits <= 10 and len(cut) != D << site_bits:  # (else: the library's error)
             raise ValueError("cut size != collections << site_bits")
-        wb = CwMapWeftBatch(self._map_batch(off, [_ptr(x) for x in (i, c, ci, k)], key_bits,
-                                            token_bits), site_shift, site_bits, _ptr(cut))
-        ko = np.zeros(D + 1, np.uint64)
-        NK = N + (D << site_bits)  # + one [id] node per named site
-        cap = max(NK, 1)
-        src = np.zeros(cap, np.uint32)
-        out = MapResult(np.zeros(cap + 1, np.uint64), np.zeros(cap, np.uint32),
-                        np.zeros(cap, np.uint64), np.zeros(cap, np.int64),
-                        np.zeros(NK + cap, np.uint32), np.zeros(max(D, 1), np.uint32))
-        r = CwMapWeftResult(ko.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src),
-                            CwMapResult(cap, 0, _ptr(out.seg_offsets), _ptr(out.seg_coll),
-                                        _ptr(out.seg_key), _ptr(out.seg_active),
-                                        _ptr(out.seg_perm), _ptr(out.status)))
-        self._check(self._L.cw_weft_maps(self._h, C.byref(wb), C.byref(r), CW_MEM_HOST),
-                    "cw_weft_maps")
-        S, M = int(r.maps.n_segs), int(ko[-1])
-        return MapWeftResult(ko, src[:M], MapResult(
-            out.seg_offsets[:S + 1], out.seg_coll[:S], out.seg_key[:S], out.seg_active[:S],
-            out.seg_perm[:M + S], out.status[:D]))
+        wb = CwMapWeftBatch(self._map_batch(off, [_ptr(x) for x in cols], key_bits, token_bits),
+                            site_shift, site_bits, _ptr(cut))
+        # + one [id] node per named site
+        return MapWeftResult(*self._kept_maps_host("cw_weft_maps", wb, CwMapWeftResult,
+                                                   N + (D << site_bits), D))
 
     # --- render: causal->edn / count of woven lists and maps -----------------------
     def render_lists_device(self, offsets, perm_ptr, bits_ptr, src_ptr=None, value_ptr=None,
@@ -945,12 +842,11 @@ class Weaver:
         weave_perm (uint32, or uint16 with perm16), visible_bits, the value
         column and the outputs rendered_src / rendered_value (None = NULL).
         Returns the rendered offsets (uint64[D+1])."""
-        off = np.ascontiguousarray(offsets, np.uint64)
-        vp = lambda p: C.c_void_p(p) if p else None
-        b = CwRenderBatch(len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_uint64)), vp(perm_ptr),
-                          vp(bits_ptr), int(perm16), value_size, vp(value_ptr))
+        off = _u64(offsets)
+        b = CwRenderBatch(len(off) - 1, _u64p(off), _vp(perm_ptr), _vp(bits_ptr), int(perm16),
+                          value_size, _vp(value_ptr))
         ro = np.zeros(len(off), np.uint64)
-        r = CwRenderResult(ro.ctypes.data_as(C.POINTER(C.c_uint64)), vp(src_ptr), vp(out_value_ptr))
+        r = CwRenderResult(_u64p(ro), _vp(src_ptr), _vp(out_value_ptr))
         self._check(self._L.cw_render_lists(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
                     "cw_render_lists")
         return ro
@@ -959,7 +855,7 @@ class Weaver:
         """Host-memory call of cw_render_lists: the rendered nodes of every
         document from a weave's weave_perm (uint32, or uint16: perm16) and
         visible_bits; value: one word of 1, 2, 4 or 8 bytes per node."""
-        off = np.ascontiguousarray(offsets, np.uint64)
+        off = _u64(offsets)
         perm = np.ascontiguousarray(weave_perm)
         if perm.dtype != np.uint16:
             perm = np.ascontiguousarray(perm, np.uint32)
@@ -971,10 +867,10 @@ class Weaver:
         ro = np.zeros(len(off), np.uint64)
         src = np.zeros(max(N, 1), np.uint32)
         oval = None if val is None else np.zeros(max(N, 1), val.dtype)
-        b = CwRenderBatch(len(off) - 1, off.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(perm),
-                          _ptr(bits), int(perm.dtype == np.uint16),
-                          0 if val is None else val.dtype.itemsize, _ptr(val))
-        r = CwRenderResult(ro.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(src), _ptr(oval))
+        b = CwRenderBatch(len(off) - 1, _u64p(off), _ptr(perm), _ptr(bits),
+                          int(perm.dtype == np.uint16), 0 if val is None else val.dtype.itemsize,
+                          _ptr(val))
+        r = CwRenderResult(_u64p(ro), _ptr(src), _ptr(oval))
         self._check(self._L.cw_render_lists(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
                     "cw_render_lists")
         R = int(ro[-1])
@@ -988,14 +884,11 @@ class Weaver:
         outputs entry_key / entry_src / entry_value (None = NULL); coll_offsets
         (host) only with a value column.  Returns the entry offsets
         (uint64[n_colls+1])."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        co = None if coll_offsets is None else np.ascontiguousarray(coll_offsets, np.uint64)
-        b = CwMapRenderBatch(n_colls, n_segs, vp(coll_ptr), vp(key_ptr), vp(active_ptr),
-                             None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint64)),
-                             value_size, vp(value_ptr))
+        co = None if coll_offsets is None else _u64(coll_offsets)
+        b = CwMapRenderBatch(n_colls, n_segs, _vp(coll_ptr), _vp(key_ptr), _vp(active_ptr),
+                             _u64p(co), value_size, _vp(value_ptr))
         eo = np.zeros(n_colls + 1, np.uint64)
-        r = CwMapRenderResult(eo.ctypes.data_as(C.POINTER(C.c_uint64)), vp(key_out_ptr), vp(src_ptr),
-                              vp(out_value_ptr))
+        r = CwMapRenderResult(_u64p(eo), _vp(key_out_ptr), _vp(src_ptr), _vp(out_value_ptr))
         self._check(self._L.cw_render_maps(self._h, C.byref(b), C.byref(r), CW_MEM_DEVICE),
                     "cw_render_maps")
         return eo
@@ -1014,17 +907,15 @@ class Weaver:
         val = _value_column(value)
         co = None
         if val is not None:
-            co = np.ascontiguousarray(coll_offsets, np.uint64)
+            co = _u64(coll_offsets)
             if len(co) != n_colls + 1 or int(co[-1]) != len(val):
                 raise ValueError("coll_offsets / value sizes")
         eo = np.zeros(n_colls + 1, np.uint64)
         key, src = np.zeros(max(S, 1), np.uint64), np.zeros(max(S, 1), np.uint32)
         oval = None if val is None else np.zeros(max(S, 1), val.dtype)
-        b = CwMapRenderBatch(n_colls, S, _ptr(sc), _ptr(sk), _ptr(sa),
-                             None if co is None else co.ctypes.data_as(C.POINTER(C.c_uint64)),
+        b = CwMapRenderBatch(n_colls, S, _ptr(sc), _ptr(sk), _ptr(sa), _u64p(co),
                              0 if val is None else val.dtype.itemsize, _ptr(val))
-        r = CwMapRenderResult(eo.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(key), _ptr(src),
-                              _ptr(oval))
+        r = CwMapRenderResult(_u64p(eo), _ptr(key), _ptr(src), _ptr(oval))
         self._check(self._L.cw_render_maps(self._h, C.byref(b), C.byref(r), CW_MEM_HOST),
                     "cw_render_maps")
         R = int(eo[-1])

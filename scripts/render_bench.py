@@ -24,7 +24,6 @@ in one JSON line (also written to --out):
   are compared before anything is reported.
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -33,8 +32,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-HBM_TBS = 8.0
 
 
 def main():
@@ -47,22 +44,13 @@ def main():
     a = ap.parse_args()
     import torch
 
+    from _common import HBM_TBS, emit, list_outs, map_outs, med, timed, up
+    from _common import z as empty
     from cause_amd import abi, gen
 
-    dev = torch.device("cuda", 0)
     torch.cuda.init()
-    z = lambda n, dt: torch.empty(max(n, 1), dtype=dt, device=dev)
+    z = lambda n, dt: empty(max(n, 1), dt)
     host = lambda t, dt: t.cpu().numpy().view(dt)
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3, out
-
-    med = lambda t: {"median": round(float(np.median(t)), 3), "min": round(float(np.min(t)), 3),
-                     "all": [round(x, 3) for x in t]}
 
     def kernels(w, fn, names):
         w.reset_kernel_stats()
@@ -89,15 +77,13 @@ def main():
         off, idk, ck, kd = gen.generate(spec, 0, a.docs, nthreads=16, k32=True)
         N, D = len(idk), a.docs
         val = (np.arange(N, dtype=np.uint32) * np.uint32(2654435761)) >> np.uint32(11)  # "code points"
-        g = [torch.from_numpy(x.view(np.int32) if x.dtype == np.uint32 else x).to(dev) for x in (idk, ck, kd)]
+        g = [up(x) for x in (idk, ck, kd)]
         del idk, ck, kd
-        gval = torch.from_numpy(val.view(np.int32)).to(dev)
-        perm, bits = z(N, torch.int32), z((N + 31) // 32, torch.int32)
-        outs = {"weave_perm": perm, "visible_bits": bits, "visible_count": z(D, torch.int32),
-                "max_ts": z(D, torch.int64), "status": z(D, torch.int32)}
+        gval = up(val)
+        outs, ptrs = list_outs(N, (N + 31) // 32, D)
+        perm, bits = outs["weave_perm"], outs["visible_bits"]
         torch.cuda.synchronize()
-        w.weave_lists_k32_device(off, g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), lay,
-                                 {k: v.data_ptr() for k, v in outs.items()})
+        w.weave_lists_k32_device(off, g[0].data_ptr(), g[1].data_ptr(), g[2].data_ptr(), lay, ptrs)
         torch.cuda.synchronize()
         assert int(outs["status"].max().item()) == 0
         del g
@@ -135,14 +121,12 @@ def main():
         off, idk, ck, ci, kd = gen.generate_maps(spec, 0, a.colls, nthreads=16)
         N, D = len(idk), a.colls
         val = (np.arange(N, dtype=np.uint32) * np.uint32(2654435761)) >> np.uint32(11)
-        g = [torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).to(dev) for x in (idk, ck, ci, kd)]
+        g = [up(x) for x in (idk, ck, ci, kd)]
         del idk, ck, ci, kd
-        gval = torch.from_numpy(val.view(np.int32)).to(dev)
-        o = {"seg_offsets": z(N + 1, torch.int64), "seg_coll": z(N, torch.int32), "seg_key": z(N, torch.int64),
-             "seg_active": z(N, torch.int64), "seg_perm": z(2 * N, torch.int32), "status": z(D, torch.int32)}
+        gval = up(val)
+        o, ptrs = map_outs(N, N, D)
         torch.cuda.synchronize()
-        S = w.weave_maps_device(off, [x.data_ptr() for x in g], tb, lay.key_bits,
-                                {k: v.data_ptr() for k, v in o.items()}, N)
+        S = w.weave_maps_device(off, [x.data_ptr() for x in g], tb, lay.key_bits, ptrs, N)
         torch.cuda.synchronize()
         del g
         okey, osrc, oval = z(S, torch.int64), z(S, torch.int32), z(S, torch.int32)
@@ -198,12 +182,7 @@ def main():
     # the same kernel with fewer outputs: what the scan alone and each output cost
     line["variants"] = {k: kernels(w, fn, names[:1])[names[0]] for k, fn in variants.items()}
     w.close()
-    text = json.dumps(line)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
+    emit(line, a.out, mode="w")
 
 
 if __name__ == "__main__":

@@ -22,17 +22,13 @@ Reported, in one JSON line, all from this one process on one build:
   stage with its host round trips.
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-HBM_TBS = 8.0
 UNION = ("merge_concat", "m_idsort", "merge_count", "merge_write")
 
 
@@ -44,6 +40,7 @@ def main():
     a = ap.parse_args()
     import torch
 
+    from _common import emit, hbm, list_outs, timed, up, z
     from cause_amd import abi, gen
 
     dev = torch.device("cuda", 0)
@@ -68,7 +65,6 @@ def main():
     na, nb = both + only_a, n - only_a
     oa = (np.arange(D + 1) * na).astype(np.uint64)
     ob = (np.arange(D + 1) * nb).astype(np.uint64)
-    up = lambda x: torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).to(dev)
     val = np.arange(N, dtype=np.uint64)
     ga = [up(x[in_a]) for x in (idk, ck, kd, val)]
     gb = [up(x[in_b]) for x in (idk, ck, kd, val)]
@@ -80,20 +76,10 @@ def main():
     del doc
     gm = [gi[perm]] + [up(x)[perm] for x in (ck, kd)]
     del gi, perm
-    z = lambda m, dt: torch.empty(m, dtype=dt, device=dev)
-    o = {"weave_perm": z(NC, torch.int32), "visible_bits": z((NC + 31) // 32 + 1, torch.int32),
-         "visible_count": z(D, torch.int32), "max_ts": z(D, torch.int64), "status": z(D, torch.int32)}
+    o, outs = list_outs(NC, (NC + 31) // 32 + 1, D)
     src = z(NC, torch.int32)
-    outs = {k: v.data_ptr() for k, v in o.items()}
     pa, pb, pm = ([x.data_ptr() for x in g] for g in (ga, gb, gm))
     torch.cuda.synchronize()
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3, out
 
     w = abi.Weaver(0)
     wg = abi.Weaver(0, options={"list_merge_fused": 0})
@@ -136,9 +122,7 @@ def main():
         "what": "cw_merge_lists, config-2 documents split into two replicas, device memory",
         "docs": D, "nodes": N, "na": int(oa[-1]), "nb": int(ob[-1]), "share": a.share,
         "merged": int(mo[-1]), "steps": a.steps, "build": abi.build_id(),
-        "list_union": {"ms": round(k_ms, 4), "bytes_alg": by / launches,
-                       "tb_per_s": round(by / launches / (k_ms / 1e3) / 1e12, 3),
-                       "frac_of_hbm_peak": round(by / launches / (k_ms / 1e3) / 1e12 / HBM_TBS, 3)},
+        "list_union": hbm(k_ms, by / launches),
         "merge_ms": {"median": round(med(t_merge), 3), "all": [round(x, 3) for x in t_merge]},
         "weave_ms": {"median": round(med(t_weave), 3), "all": [round(x, 3) for x in t_weave]},
         "overhead_ms": round(med(t_merge) - k_ms - med(t_weave), 3),
@@ -147,7 +131,7 @@ def main():
                              **{k: round(v, 3) for k, v in g_union.items()}},
         "general_stage_ms": round(med(t_general) - med(t_weave), 3),
     }
-    print(json.dumps(line), flush=True)
+    emit(line)
 
 
 if __name__ == "__main__":

@@ -27,32 +27,13 @@ given):
   before the fused route.
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-HBM_TBS = 8.0
-
-
-def quantile_cuts(idk, D, n, lay, q=0.5):
-    """cut u64[D << site_bits]: per document and site rank the largest id whose
-    ts is <= the document's q-quantile ts (0: the site has none)."""
-    S = 1 << lay.site_bits
-    ids = idk.reshape(D, n)
-    ts = ids >> np.uint64(lay.ts_shift)
-    T = np.sort(ts, axis=1)[:, min(int(q * n), n - 1)]
-    older = np.where(ts <= T[:, None], ids, np.uint64(0))
-    site = (ids >> np.uint64(lay.site_shift)) & np.uint64(S - 1)
-    cut = np.zeros((D, S), np.uint64)
-    for r in range(S):
-        cut[:, r] = np.where(site == np.uint64(r), older, np.uint64(0)).max(axis=1)
-    return cut.reshape(-1)
 
 
 def main():
@@ -63,26 +44,18 @@ def main():
     a = ap.parse_args()
     import torch
 
+    from _common import emit, hbm, kernel_ms, list_outs, med, quantile_cuts, timed, up, z
     from cause_amd import abi, gen
 
-    dev = torch.device("cuda", 0)
     torch.cuda.init()
     spec = gen.CONFIG2
     lay = spec.layout()
     off, idk, ck, kd = gen.generate(spec, 0, a.docs, nthreads=16)
     N, D, sb = len(idk), a.docs, lay.site_bits
-    cut = quantile_cuts(idk, D, spec.doc_size, lay)
+    cuts = lambda q: quantile_cuts(idk, D, spec.doc_size, lay.ts_shift, lay.site_shift, sb, q)
+    cut = cuts(0.5)
     has_dev = hasattr(abi.lib(), "cw_weft_lists_dev")
 
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3, out
-
-    med = lambda t: {"median": round(float(np.median(t)), 3), "min": round(float(np.min(t)), 3),
-                     "all": [round(x, 3) for x in t]}
     line = {"what": "list weft, config-2 documents cut at their median ts",
             "docs": D, "nodes": N, "site_bits": sb, "steps": a.steps, "build": abi.build_id()}
 
@@ -100,29 +73,13 @@ def main():
             wh.set_profiling(False)
             line["host_list_weft_ms"] = round(wh.kernel_stats()["list_weft"][1], 4)
     if has_dev:
-        up = lambda x: torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).to(dev)
         g = [up(x) for x in (idk, ck, kd)]
-        gcut, gcut2 = up(cut), up(quantile_cuts(idk, D, spec.doc_size, lay, 0.75))
-        z = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
+        gcut, gcut2 = up(cut), up(cuts(0.75))
         cap = N + (D << sb)
-        o = {"weave_perm": z(cap, torch.int32), "visible_bits": z((cap + 31) // 32, torch.int32),
-             "visible_count": z(D, torch.int32), "max_ts": z(D, torch.int64),
-             "status": z(D, torch.int32), "yarn_perm": z(cap, torch.int32)}
+        o, outs = list_outs(cap, (cap + 31) // 32, D, yarns=True)
         src = z(cap, torch.int32)
-        outs = {k: v.data_ptr() for k, v in o.items()}
         ptrs = [x.data_ptr() for x in g]
         torch.cuda.synchronize()
-
-        def kernel_ms(w, name, fn):
-            """Mean event time and algorithmic bytes of one kernel stat over --steps calls."""
-            w.set_profile_only(name)
-            w.reset_kernel_stats()
-            w.set_profiling(True)
-            for _ in range(a.steps):
-                fn()
-            w.set_profiling(False)
-            launches, ms, by = w.kernel_stats()[name]
-            return ms / launches, by / launches
 
         # a context each: both calls cache the document tables by layout, and
         # the kept layout is not the input's
@@ -137,7 +94,7 @@ def main():
         for _ in range(a.steps):
             t_weft.append(timed(weft)[0])
             t_weave.append(timed(weave)[0])
-        k_ms, k_by = kernel_ms(w, "list_weft", weft)
+        k_ms, k_by = kernel_ms(w, "list_weft", weft, a.steps)
         t_fresh = [timed(lambda: weft(w, (gcut2, gcut)[k % 2]))[0] for k in range(a.steps)]
         w.close()
         w2.close()
@@ -146,12 +103,10 @@ def main():
                 kg = weft(wg)
             assert np.array_equal(kg, ko)
             t_general = [timed(lambda: weft(wg))[0] for _ in range(a.steps)]
-            c_ms, _ = kernel_ms(wg, "weft_count", lambda: weft(wg))
-            r_ms, _ = kernel_ms(wg, "weft_write", lambda: weft(wg))
+            c_ms, _ = kernel_ms(wg, "weft_count", lambda: weft(wg), a.steps)
+            r_ms, _ = kernel_ms(wg, "weft_write", lambda: weft(wg), a.steps)
         line.update({
-            "list_weft": {"ms": round(k_ms, 4), "bytes_alg": k_by,
-                          "tb_per_s": round(k_by / (k_ms / 1e3) / 1e12, 3),
-                          "frac_of_hbm_peak": round(k_by / (k_ms / 1e3) / 1e12 / HBM_TBS, 3)},
+            "list_weft": hbm(k_ms, k_by),
             "dev_ms": med(t_weft),
             "dev_fresh_cuts_ms": med(t_fresh),
             "weave_ms": med(t_weave),
@@ -159,12 +114,7 @@ def main():
             "general_kernels_ms": {"weft_count": round(c_ms, 4), "weft_write": round(r_ms, 4),
                                    "sum": round(c_ms + r_ms, 4)},
         })
-    text = json.dumps(line)
-    print(text, flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write(text + "\n")
+    emit(line, a.out)
 
 
 if __name__ == "__main__":

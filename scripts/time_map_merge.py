@@ -17,17 +17,13 @@ everything resident in device memory.  Reported, in one JSON line:
   once, for the record.
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-
-HBM_TBS = 8.0
 
 
 def main():
@@ -38,6 +34,7 @@ def main():
     a = ap.parse_args()
     import torch
 
+    from _common import emit, hbm, map_outs, timed, up, z
     from cause_amd import abi, gen
 
     dev = torch.device("cuda", 0)
@@ -52,7 +49,6 @@ def main():
     o64 = off.astype(np.int64)
     offs = lambda m: np.concatenate([[0], np.cumsum(m)])[o64].astype(np.uint64)
     oa, ob = offs(in_a), offs(in_b)
-    up = lambda x: torch.from_numpy(x.view(np.int64) if x.dtype == np.uint64 else x).to(dev)
     val = np.arange(N, dtype=np.uint64)
     ga = [up(x[in_a]) for x in (idk, ck, ci, kd, val)]
     gb = [up(x[in_b]) for x in (idk, ck, ci, kd, val)]
@@ -65,22 +61,11 @@ def main():
     del coll
     gm = [gi[order]] + [up(x)[order] for x in (ck, ci, kd)]
     del gi, order
-    z = lambda n, dt: torch.empty(n, dtype=dt, device=dev)
     cap = NC
-    o = {"seg_offsets": z(cap + 1, torch.int64), "seg_coll": z(cap, torch.int32),
-         "seg_key": z(cap, torch.int64), "seg_active": z(cap, torch.int64),
-         "seg_perm": z(NC + cap, torch.int32), "status": z(D, torch.int32)}
+    o, outs = map_outs(cap, NC, D)
     src = z(NC, torch.int32)
-    outs = {k: v.data_ptr() for k, v in o.items()}
     pa, pb, pm = ([x.data_ptr() for x in g] for g in (ga, gb, gm))
     torch.cuda.synchronize()
-
-    def timed(fn):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        out = fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3, out
 
     w = abi.Weaver(0)
     merge = lambda ww=w: ww.merge_maps_device(oa, pa, ob, pb, tb, lay.key_bits, src.data_ptr(), outs, cap)
@@ -108,14 +93,12 @@ def main():
         "what": "cw_merge_maps, config-4 collections split into two replicas, device memory",
         "colls": D, "nodes": N, "na": Na, "nb": Nb, "share": a.share, "merged": int(mo[-1]),
         "key_weaves": S, "steps": a.steps, "build": abi.build_id(),
-        "map_union": {"ms": round(k_ms, 4), "bytes_alg": by / launches,
-                      "tb_per_s": round(by / launches / (k_ms / 1e3) / 1e12, 3),
-                      "frac_of_hbm_peak": round(by / launches / (k_ms / 1e3) / 1e12 / HBM_TBS, 3)},
+        "map_union": hbm(k_ms, by / launches),
         "merge_ms": {"median": round(float(np.median(t_merge)), 3), "all": [round(x, 3) for x in t_merge]},
         "weave_ms": {"median": round(float(np.median(t_weave)), 3), "all": [round(x, 3) for x in t_weave]},
         "general_ms": round(t_general, 3),
     }
-    print(json.dumps(line), flush=True)
+    emit(line)
 
 
 if __name__ == "__main__":

@@ -16,6 +16,10 @@ contract with the library is still plain text that can be read:
 
 check_twins() returns the list of problems (empty = in line); the tests feed
 it the committed sources and deliberately drifted copies.
+
+The header parsers read every struct (nested ones, char arrays, several names
+in one declaration) and every prototype: tests/test_abi_header.py holds the
+Python twin, cause_amd/abi.py, against header_layouts and header_prototypes.
 """
 from __future__ import annotations
 
@@ -34,7 +38,7 @@ LAYOUTS = {"LIST_BATCH": "cw_list_batch", "LIST_BATCH_K128": "cw_list_batch_k128
 # C scalar type -> (Panama carrier, size)
 CARRIER = {"uint64_t": ("JAVA_LONG", 8), "int64_t": ("JAVA_LONG", 8), "size_t": ("JAVA_LONG", 8),
            "uint32_t": ("JAVA_INT", 4), "int32_t": ("JAVA_INT", 4), "int": ("JAVA_INT", 4),
-           "uint8_t": ("JAVA_BYTE", 1), "char": ("JAVA_BYTE", 1)}
+           "uint8_t": ("JAVA_BYTE", 1), "char": ("JAVA_BYTE", 1), "double": ("JAVA_DOUBLE", 8)}
 
 
 def _strip_c_comments(src: str) -> str:
@@ -56,6 +60,8 @@ def header_constants(src: str) -> dict:
 
 
 def _c_field(decl: str):
+    """(name, carrier, size) of a one-name scalar or pointer member (the model
+    tests size their own structs with it); header_layouts reads every member."""
     m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+)\s*", decl)
     if not m:
         return None
@@ -63,51 +69,91 @@ def _c_field(decl: str):
     if ptr:
         return name, "ADDRESS", 8
     if typ not in CARRIER:
-        return name, None, None  # a nested struct: not mirrored by the Java layouts
+        return name, None, None  # a nested struct
     return (name,) + CARRIER[typ]
+
+
+def _c_fields(decl: str, layouts: dict):
+    """[(name, carrier, size, alignment)] of one member declaration (several
+    names after one type, a char[n]), or None when it is not understood.  A
+    member that is itself one of the structs parsed so far has that typedef's
+    name as its carrier (the Java layouts mirror no such struct)."""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\*?)\s*(\w+(?:\s*\[\d+\])?(?:\s*,\s*\w+)*)\s*", decl)
+    if not m:
+        return None
+    typ, ptr, names = m.groups()
+    out = []
+    for name in names.split(","):
+        name, _, count = name.strip().partition("[")
+        count = int(count.rstrip("] ")) if count else 0
+        if ptr:
+            car, size, align = "ADDRESS", 8, 8
+        elif typ in CARRIER:
+            car, size = CARRIER[typ]
+            align = size
+        elif typ in layouts:
+            car, (_, size, align) = typ, layouts[typ]
+        else:
+            return None
+        out.append((name.strip(), f"{car}[{count}]", size * count, align) if count else
+                   (name, car, size, align))
+    return out
+
+
+def header_layouts(src: str) -> dict:
+    """typedef name -> ([(field, carrier, size, offset)], size, alignment) of
+    every struct the header defines, with natural alignment."""
+    s = _strip_c_comments(src)
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", s, flags=re.S):
+        fields, off, big, ok = [], 0, 1, True
+        for decl in body.split(";"):
+            if not decl.strip():
+                continue
+            fs = _c_fields(decl, out)
+            if fs is None:
+                ok = False
+                break
+            for fname, car, size, align in fs:
+                off = (off + align - 1) // align * align
+                fields.append((fname, car, size, off))
+                off += size
+                big = max(big, align)
+        if ok:
+            out[name] = (fields, (off + big - 1) // big * big, big)
+    return out
 
 
 def header_structs(src: str) -> dict:
     """typedef name -> [(field, carrier, size, offset)] with natural alignment."""
-    s = _strip_c_comments(src)
+    return {name: fields for name, (fields, _, _) in header_layouts(src).items()}
+
+
+def _c_type(text: str, named: bool) -> str:
+    """'const uint32_t *keys' -> 'uint32_t *': a type without const and name."""
+    words = text.replace("*", " * ").replace("const", " ").split()
+    if named and words[-1] != "*":
+        words = words[:-1]
+    return " ".join(words)
+
+
+def header_prototypes(src: str) -> dict:
+    """cw_* prototype -> (return type, [parameter types]) as C text ('int',
+    'char *', 'cw_list_batch *', 'cw_ctx * *')."""
+    s = re.sub(r"(?m)^\s*#.*$", ";", _strip_c_comments(src))  # preprocessor lines end a statement
+    s = " ".join(s.split())
     out = {}
-    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", s, flags=re.S):
-        fields, off, ok = [], 0, True
-        for decl in body.split(";"):
-            if not decl.strip():
-                continue
-            f = _c_field(decl)
-            if f is None or f[1] is None:
-                ok = False
-                break
-            fname, car, size = f
-            off = (off + size - 1) // size * size
-            fields.append((fname, car, size, off))
-            off += size
-        if ok:
-            out[name] = fields
+    for ret, name, params in re.findall(r"(?:(?<=[;}{])|^)\s*([\w\s\*]+?)\s*\b(cw_\w+)\s*\(([^)]*)\)\s*;", s):
+        ps = [_c_type(p, True) for p in params.split(",") if p.strip() and p.strip() != "void"]
+        out[name] = (_c_type(ret, False), ps)
     return out
 
 
 def header_functions(src: str) -> dict:
     """cw_* prototype -> (return carrier or 'void', [parameter carriers])."""
-    s = re.sub(r"(?m)^\s*#.*$", ";", _strip_c_comments(src))  # preprocessor lines end a statement
-    s = " ".join(s.split())
-    out = {}
-    for ret, name, params in re.findall(r"(?:(?<=[;}{])|^)\s*([\w\s\*]+?)\s*\b(cw_\w+)\s*\(([^)]*)\)\s*;", s):
-        ret = ret.strip()
-        rc = "void" if ret == "void" else ("ADDRESS" if "*" in ret else CARRIER.get(ret.split()[-1], (None,))[0])
-        ps = []
-        for p in params.split(","):
-            p = p.strip()
-            if not p or p == "void":
-                continue
-            if "*" in p:
-                ps.append("ADDRESS")
-            else:
-                ps.append(CARRIER.get(p.replace("const ", "").split()[0], (None,))[0])
-        out[name] = (rc, ps)
-    return out
+    car = lambda t: "void" if t == "void" else ("ADDRESS" if "*" in t else CARRIER.get(t, (None,))[0])
+    return {name: (car(ret), [car(p) for p in ps])
+            for name, (ret, ps) in header_prototypes(src).items()}
 
 
 def java_constants(src: str) -> dict:
