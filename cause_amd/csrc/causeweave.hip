@@ -44,6 +44,7 @@
 #include "causeweave.h"
 #include "cw_internal.h"
 #include "lookback.h"
+#include "xplan.h"
 
 using namespace cw;
 
@@ -4490,7 +4491,6 @@ struct cw_ctx {
   uint32_t os_epoch = 0;
   const uint32_t *last_dyn = nullptr;  // the last HBM walk's continued-sublist counters
   uint32_t last_dyn_n = 0;             // ... (one per document of that walk)
-  uint32_t x_iters = 0;            // synthetic-list weaves of the last exact path (exact.hip)
   uint32_t xfold = 0;              // xfold: documents with an early node take the serial fold
   uint32_t x_round_cap = 48;       // x_round_cap: anchor rounds before a small still-moving
                                    // document takes the serial fold (exact.hip X_ROUND_CAP)

@@ -80,7 +80,6 @@ constexpr uint32_t X_MASK = CW_STATUS_ROOT | CW_STATUS_ORPHAN | CW_STATUS_NON_LA
 // batch the pipeline found inconsistent (ids wider than the declared key_bits)
 constexpr uint32_t X_SKIP = CW_STATUS_DUP | CW_STATUS_KEY_RANGE | CW_STATUS_INTERNAL;
 constexpr uint32_t XFOLD_MAX = 1u << 22;     // xfold: the serial fold's largest document
-constexpr uint32_t X_NONE = 0xFFFFFFFFu;     // not on the synthetic path
 constexpr uint32_t MT_MAX = 0xFFFFFFFFu;     // min-tree padding ("no node")
 
 // A node weave-asap? never holds for: its cause is absent, or not older than
@@ -480,28 +479,23 @@ __global__ __launch_bounds__(256) void k_xsyn_build(
 }
 
 // Positions of a woven synthetic list: G[x] = the global synthetic index at
-// global position x, pos[g] = the position of g.  AUX[x] (mode 0, the static
-// forest) = 0 where the node is structurally non-special, else G[x] -- "the
-// first later position < s" then ends a special run; (mode 1, phase 2) =
-// G[x] where the node is non-special, else MT_MAX.  posold != nullptr: count
-// the positions that changed (phase 2's fixed point).
+// global position x, pos[g] = the position of g.  AUX[x] = 0 where the node is
+// structurally non-special, else G[x] -- "the first later position < s" then
+// ends a special run.
 __global__ __launch_bounds__(256) void k_xs_pos(
     const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ tile_doc,
     const uint32_t *__restrict__ doc_off, const uint32_t *__restrict__ sbase,
-    const uint8_t *__restrict__ only, const uint32_t *__restrict__ wperm,
-    const uint8_t *__restrict__ skd, const uint8_t *__restrict__ xk, uint32_t mode,
-    uint32_t *__restrict__ G, uint32_t *__restrict__ AUX, uint32_t *__restrict__ pos,
-    const uint32_t *__restrict__ posold, uint32_t *__restrict__ ctl) {
+    const uint32_t *__restrict__ wperm, const uint8_t *__restrict__ skd, uint32_t *__restrict__ G,
+    uint32_t *__restrict__ AUX, uint32_t *__restrict__ pos, uint32_t *__restrict__ ctl) {
   const uint32_t t = blockIdx.x, f = tile_doc[t], sb = sbase[f];
-  if (sb == X_NONE || (only && !only[f])) return;
+  if (sb == X_NONE) return;
   const uint32_t base = doc_off[f], n = doc_off[f + 1] - base;
-  uint32_t changed = 0;
   for (uint32_t i = tile_start[t] + threadIdx.x; i < tile_start[t + 1]; i += blockDim.x) {
     const uint32_t q = i - base, x = sb + 1 + q, s = wperm[x];
     if (q == 0) {
       G[sb] = sb;
       pos[sb] = sb;
-      AUX[sb] = mode == 0 ? 0u : sb;
+      AUX[sb] = 0u;
     }
     if (s < 1 || s > n) {
       atomicOr(&ctl[1], 1u);  // H is always first: a later position that holds it is an error
@@ -509,14 +503,8 @@ __global__ __launch_bounds__(256) void k_xs_pos(
     }
     const uint32_t g = sb + s;
     G[x] = g;
-    if (posold && posold[g] != x) changed++;
     pos[g] = x;
-    const bool ns = mode == 0 ? (skd[g] & KIND_CLASS) == 0 : (xk[base + s - 1] & KIND_CLASS) == 0;
-    AUX[x] = mode == 0 ? (ns ? 0u : g) : (ns ? g : MT_MAX);
-  }
-  if (posold) {
-    for (int o = 32; o > 0; o >>= 1) changed += __shfl_xor(changed, o, 64);
-    if ((threadIdx.x & 63) == 0 && changed) atomicAdd(&ctl[0], changed);
+    AUX[x] = (skd[g] & KIND_CLASS) == 0 ? 0u : g;
   }
 }
 
@@ -1256,6 +1244,385 @@ int mt_build(cw_ctx *c, const char *name, const uint32_t *a, uint64_t len, XMinT
   return check_launch(c, "mt_level");
 }
 
+// A synthetic layout on the device: its plan (xplan.h), each list's parents,
+// kinds, weave and render bits by synthetic index, and G / AUX by position,
+// level 0 of the two min-trees.
+struct XLayout {
+  XPlan plan;
+  uint64_t NP = 0;  // min-tree level 0: NS padded to a multiple of 16, and 16 more
+  uint32_t *d_sb = nullptr, *spar = nullptr, *wperm = nullptr, *wbits = nullptr, *G = nullptr, *AUX = nullptr;
+  uint8_t *skd = nullptr;
+  bool bits_read = false;  // the emission reads the bits: cleared before each weave
+};
+
+struct XNames {
+  const char *sb, *spar, *skd, *wperm, *wbits, *G, *aux;
+};
+constexpr XNames X_LAYOUT1{"x_sbase", "x_spar", "x_skd", "x_wperm", "x_wbits", "x_G", "x_aux"};
+constexpr XNames X_LAYOUT2{"x_sbase2", "x_spar2", "x_skd2", "x_wperm2", "x_wbits2", "x_G2", "x_aux2"};
+
+// The buffers of L->plan (the bases uploaded: a blocking copy).  False: out of
+// device memory.
+bool x_layout(cw_ctx *c, const XNames &nm, bool bits_read, XLayout *L) {
+  const uint64_t NS = L->plan.NS;
+  L->NP = ((NS + 15) & ~15ull) + 16;
+  L->bits_read = bits_read;
+  L->d_sb = x_upload(c, nm.sb, L->plan.sb);
+  L->spar = scratch_t<uint32_t>(c, nm.spar, NS), L->wperm = scratch_t<uint32_t>(c, nm.wperm, NS);
+  L->skd = scratch_t<uint8_t>(c, nm.skd, NS);
+  L->wbits = scratch_t<uint32_t>(c, nm.wbits, NS / 32 + 1);
+  L->G = scratch_t<uint32_t>(c, nm.G, L->NP), L->AUX = scratch_t<uint32_t>(c, nm.aux, L->NP);
+  return L->d_sb && L->spar && L->wperm && L->skd && L->wbits && L->G && L->AUX;
+}
+
+// One call of exact_weave_flagged: its arguments, the flagged documents'
+// tables, and what its stages hand on.
+struct XCall {
+  cw_ctx *c;
+  uint32_t F;
+  const std::vector<uint64_t> &xoff;
+  const uint32_t *xpar;
+  const uint8_t *xk, *early;
+  const uint32_t *sval;
+  const uint64_t *d_oof;
+  const uint32_t *d_odoc;
+  cw_list_result *out;
+  uint32_t NX, T = 0;
+  uint32_t *tile_start = nullptr, *tile_doc = nullptr, *sub_off = nullptr;  // x_tables
+  // x_plan_call
+  std::vector<uint8_t> run, x2;  // per document: takes the serial fold / the anchor rounds
+  bool any_serial = false, any_x2 = false;
+  uint64_t A = 0;     // appended nodes of the documents in layout 1
+  uint32_t nmax = 1;  // the largest document in layout 2
+  XLayout L1, L2;
+  // x_static
+  uint8_t *d_x2 = nullptr;
+  uint32_t *ctl = nullptr;                  // [1]: a kernel found a weave inconsistent
+  uint32_t *wvc = nullptr, *wst = nullptr;  // a group's counts and status (never read)
+  uint32_t *posA = nullptr, *ctop = nullptr, *Nof = nullptr, *tcnt = nullptr;
+  // x_resolve
+  uint32_t *app_list = nullptr, *app_doc = nullptr;
+};
+
+// The flagged documents' tables (again, after a group's): on the device, and
+// where they lie.
+int x_tables(XCall &x) {
+  if (ensure_tables(x.c, x.F, x.xoff.data())) return -1;
+  x.tile_start = dev_tab(x.c, "t_tile_start");
+  x.tile_doc = dev_tab(x.c, "t_tile_doc");
+  x.sub_off = dev_tab(x.c, "t_doc_off");
+  x.T = x.c->tab.T;
+  return 0;
+}
+
+// The per-document flags read back, then both layouts: layout 1 (n + 1 slots)
+// for every document but those the option xfold leaves to the serial fold,
+// layout 2 (2n + 1) for the ones among them with an early node.
+int x_plan_call(XCall &x, const uint8_t *dearly, const uint32_t *dapp) {
+  cw_ctx *c = x.c;
+  const uint32_t F = x.F;
+  std::vector<uint8_t> h_early(F), part(F, 1);
+  std::vector<uint32_t> h_app(F);
+  HIPCHK(c, hipMemcpyAsync(h_early.data(), dearly, F, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(h_app.data(), dapp, (size_t)F * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  x.run.assign(F, 0);
+  x.x2.assign(F, 0);
+  for (uint32_t f = 0; f < F; f++) {
+    const uint64_t n = x.xoff[f + 1] - x.xoff[f];
+    if (c->xfold && h_early[f] && n <= XFOLD_MAX) {  // xfold: the serial fold (cross-check)
+      x.run[f] = 1;
+      part[f] = 0;
+      x.any_serial = true;
+      continue;
+    }
+    x.A += h_app[f];
+    if (!h_early[f]) continue;
+    x.x2[f] = 1;
+    x.any_x2 = true;
+    x.nmax = std::max<uint32_t>(x.nmax, (uint32_t)n);
+  }
+  x.L1.plan = x_plan(F, x.xoff.data(), part.data(), h_early.data(), false, c->giant_min, LINK_IDX);
+  if (x.L1.plan.NS >= 0xFFFFFFF0ull - 16)
+    return fail(c, "exact path: %llu synthetic nodes", (unsigned long long)x.L1.plan.NS);
+  if (x.any_x2) x.L2.plan = x_plan(F, x.xoff.data(), x.x2.data(), x.x2.data(), true, c->giant_min, LINK_IDX);
+  if (x.L2.plan.NS >= 0xFFFFFFF0ull - 16)
+    return fail(c, "exact path: %llu layout-2 nodes", (unsigned long long)x.L2.plan.NS);
+  return 0;
+}
+
+// The synthetic lists of L's groups that woven(g) holds for, each group in one
+// weave_tail; then the flagged documents' tables again.
+template <class Pred>
+int x_weave_groups(XCall &x, const XLayout &L, Pred woven) {
+  cw_ctx *c = x.c;
+  for (const XGroup &g : L.plan.groups) {
+    if (!woven(g)) continue;
+    const uint64_t Dg = g.off.size() - 1, Ng = g.off.back();
+    if (ensure_tables(c, Dg, g.off.data(), g.giant)) return -1;
+    HIPCHK(c, hipMemsetAsync(x.wst, 0, Dg * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(x.wvc, 0, Dg * 4, c->stream));
+    if (L.bits_read) HIPCHK(c, hipMemsetAsync(L.wbits + g.base / 32, 0, (Ng + 31) / 32 * 4, c->stream));
+    cw_list_result sr{};
+    sr.weave_perm = L.wperm + g.base;
+    sr.visible_bits = L.wbits + g.base / 32;
+    sr.visible_count = x.wvc;
+    sr.status = x.wst;
+    if (weave_tail(c, Dg, (uint32_t)Ng, g.giant, L.spar + g.base, L.skd + g.base, nullptr, nullptr, nullptr,
+                   0, &sr))
+      return -1;
+  }
+  return x_tables(x);
+}
+
+// G and AUX of a woven layout: cleared, then written by its positions kernel
+// (launch(), `bytes` of traffic).
+template <class K>
+int x_positions(cw_ctx *c, const XLayout &L, double bytes, K launch) {
+  HIPCHK(c, hipMemsetAsync(L.G, 0xFF, L.NP * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(L.AUX, 0xFF, L.NP * 4, c->stream));
+  Launch l(c, "xsyn_pos", bytes);
+  launch();
+  return check_launch(c, "xsyn_pos");
+}
+
+// Phase 1: layout 1 on the device, the static forest and its weave.
+int x_static(XCall &x) {
+  cw_ctx *c = x.c;
+  XLayout &L = x.L1;
+  const uint64_t NS = L.plan.NS;
+  const size_t lists = std::max(L.plan.max_lists(), x.L2.plan.max_lists());
+  const bool ok = x_layout(c, X_LAYOUT1, true, &L);
+  x.d_x2 = x_upload(c, "x_x2", x.x2);
+  x.posA = scratch_t<uint32_t>(c, "x_pos", NS), x.ctop = scratch_t<uint32_t>(c, "x_ctop", NS);
+  x.Nof = scratch_t<uint32_t>(c, "x_nof", NS), x.ctl = scratch_t<uint32_t>(c, "x_ctl", 2);
+  x.wvc = scratch_t<uint32_t>(c, "x_wvc", lists), x.wst = scratch_t<uint32_t>(c, "x_wst", lists);
+  const bool counts = x.A > 0 || x.any_x2;  // per-tile counts: the appended nodes, the compaction
+  if (counts) x.tcnt = scratch_t<uint32_t>(c, "x_tcnt", x.T);
+  if (!ok || !x.d_x2 || !x.posA || !x.ctop || !x.Nof || !x.ctl || !x.wvc || !x.wst || (counts && !x.tcnt))
+    return fail(c, "out of device memory (exact path, %llu synthetic nodes)", (unsigned long long)NS);
+  HIPCHK(c, hipMemsetAsync(x.ctl, 0, 8, c->stream));
+  hipLaunchKernelGGL(k_xsyn_build, dim3(x.T), dim3(256), 0, c->stream, x.tile_start, x.tile_doc, x.sub_off,
+                     L.d_sb, x.xpar, x.xk, L.spar, L.skd);
+  if (check_launch(c, "xsyn_build")) return -1;
+  return x_weave_groups(x, L, [](const XGroup &) { return true; });
+}
+
+// Phase 1, with appended nodes: every appended node's T from the static weave,
+// then the weave with each under its T.
+int x_resolve(XCall &x) {
+  if (x.A == 0) return 0;
+  cw_ctx *c = x.c;
+  const XLayout &L = x.L1;
+  const dim3 GT(x.T), B256(256);
+  if (x_positions(c, L, (double)x.NX * 13, [&] {
+        hipLaunchKernelGGL(k_xs_pos, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                           L.wperm, L.skd, L.G, L.AUX, x.posA, x.ctl);
+      }))
+    return -1;
+  XMinTree mt, mtx;
+  if (mt_build(c, "x_mtG", L.G, L.NP, &mt) || mt_build(c, "x_mtA", L.AUX, L.NP, &mtx)) return -1;
+  x.app_list = scratch_t<uint32_t>(c, "x_app", x.A);
+  x.app_doc = scratch_t<uint32_t>(c, "x_appdoc", x.A);
+  uint32_t *app_idx = scratch_t<uint32_t>(c, "x_appidx", x.NX), *Tsyn = scratch_t<uint32_t>(c, "x_T", x.A);
+  if (!x.app_list || !app_idx || !x.app_doc || !Tsyn)
+    return fail(c, "out of device memory (exact path, %llu appended nodes)", (unsigned long long)x.A);
+  const uint32_t A32 = (uint32_t)x.A;
+  const dim3 GA((A32 + 255) / 256);
+  {
+    Launch l(c, "xsyn_resolve", (double)x.NX * 16 + (double)x.A * 256);
+    hipLaunchKernelGGL(k_xctop, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb, L.spar,
+                       L.skd, x.ctop);
+    hipLaunchKernelGGL(k_xapp_count, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                       x.xpar, x.tcnt);
+    hipLaunchKernelGGL(k_xapp_scan, dim3(1), dim3(1024), 0, c->stream, x.tcnt, x.T);
+    hipLaunchKernelGGL(k_xapp_scatter, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                       x.xpar, x.tcnt, x.app_list, x.app_doc, app_idx);
+    HIPCHK(c, hipMemsetAsync(x.Nof, 0xFF, L.plan.NS * 4, c->stream));
+    hipLaunchKernelGGL(k_xres1, GA, B256, 0, c->stream, x.app_list, x.app_doc, A32, x.sub_off, L.d_sb, x.xk,
+                       x.posA, L.G, x.ctop, mt, Tsyn, x.Nof, x.ctl);
+    hipLaunchKernelGGL(k_xres2, dim3(A32), dim3(64), 0, c->stream, x.app_list, x.app_doc, A32, x.sub_off,
+                       L.d_sb, x.xpar, x.xk, x.posA, L.G, x.ctop, mt, mtx, Tsyn, x.Nof, x.ctl);
+    hipLaunchKernelGGL(k_xsyn_final, GA, B256, 0, c->stream, x.app_list, x.app_doc, A32, x.sub_off, L.d_sb,
+                       x.xk, Tsyn, L.spar, L.skd);
+  }
+  if (check_launch(c, "xsyn_resolve")) return -1;
+  return x_weave_groups(x, L, [](const XGroup &) { return true; });
+}
+
+// Phase 2's buffers: the documents still in the rounds, positions of the last
+// two weaves, a round's anchors and chains.
+struct XRounds {
+  std::vector<uint8_t> only;  // per document: still moving
+  uint8_t *d_only, *hasb, *moved;
+  uint32_t *p2A, *p2B, *xf, *anc, *jmp, *prevne;
+  uint32_t jumps;  // launches of k_x2_jump: reach (X2_JUMPS + 1)^launches >= nmax
+};
+
+// Layout 2's positions (from1: of phase 1's weave; else of layout 2's own, with
+// the per-document moved flags against posold).
+int x2_positions(XCall &x, const XRounds &r, uint32_t from1, uint32_t *pos, const uint32_t *posold) {
+  cw_ctx *c = x.c;
+  return x_positions(c, x.L2, (double)x.NX * 26, [&] {
+    hipLaunchKernelGGL(k_x2_pos, dim3(x.T), dim3(256), 0, c->stream, x.tile_start, x.tile_doc, x.sub_off,
+                       x.L1.d_sb, x.L2.d_sb, r.d_only, from1, x.L1.wperm, x.L2.wperm, x.xk, x.L2.G, x.L2.AUX,
+                       pos, posold, r.moved, x.ctl);
+  });
+}
+
+// Phase 2's set-up: layout 2 on the device, the previous non-early appended
+// node of every appended node, phase 1's weave as layout-2 positions.
+int x2_setup(XCall &x, XRounds &r) {
+  cw_ctx *c = x.c;
+  const uint32_t NX = x.NX;
+  const bool ok = x_layout(c, X_LAYOUT2, false, &x.L2);
+  r.d_only = x_upload(c, "x_only", x.x2);
+  r.p2A = scratch_t<uint32_t>(c, "x_pos2A", x.L2.plan.NS), r.p2B = scratch_t<uint32_t>(c, "x_pos2B", x.L2.plan.NS);
+  r.xf = scratch_t<uint32_t>(c, "x_xf", NX), r.anc = scratch_t<uint32_t>(c, "x_anc", NX);
+  r.jmp = scratch_t<uint32_t>(c, "x_jmp", NX), r.prevne = scratch_t<uint32_t>(c, "x_prevne", NX);
+  r.hasb = scratch_t<uint8_t>(c, "x_hasb", NX), r.moved = scratch_t<uint8_t>(c, "x_moved", x.F);
+  if (!ok || !r.d_only || !r.p2A || !r.p2B || !r.xf || !r.anc || !r.jmp || !r.prevne || !r.hasb || !r.moved)
+    return fail(c, "out of device memory (exact path rounds, %llu layout-2 nodes)",
+                (unsigned long long)x.L2.plan.NS);
+  if (x.A > 0) {
+    const uint32_t A32 = (uint32_t)x.A, C = (A32 + 255) / 256;
+    uint32_t *cmax = scratch_t<uint32_t>(c, "x_necmax", C);
+    if (!cmax) return fail(c, "out of device memory (exact path rounds)");
+    Launch l(c, "xins_prevne", (double)x.A * 14);
+    hipLaunchKernelGGL(k_x2_ne_chunk, dim3(C), dim3(256), 0, c->stream, x.app_list, A32, x.early, cmax);
+    hipLaunchKernelGGL(k_x2_ne_scan, dim3(1), dim3(1024), 0, c->stream, cmax, C);
+    hipLaunchKernelGGL(k_x2_ne_final, dim3(C), dim3(256), 0, c->stream, x.app_list, x.app_doc, A32, x.early,
+                       cmax, r.prevne);
+  }
+  if (check_launch(c, "xins_prevne")) return -1;
+  if (x2_positions(x, r, 1, r.p2A, nullptr)) return -1;
+  r.jumps = 1;
+  for (uint64_t reach = 1; reach < x.nmax; reach *= X2_JUMPS + 1) r.jumps++;
+  r.only = x.x2;
+  return 0;
+}
+
+// One anchor round: each node's insertion split in the last weave, the
+// insertion tree on layout 2, its weave for the groups that hold a moving
+// document, and the new positions against the last ones (p2A: the new ones).
+int x2_round(XCall &x, XRounds &r, uint32_t round) {
+  cw_ctx *c = x.c;
+  const XLayout &L = x.L2;
+  const dim3 GT(x.T), B256(256);
+  XMinTree mt, mtn;
+  if (mt_build(c, "x_mtG", L.G, L.NP, &mt) || mt_build(c, "x_mtA", L.AUX, L.NP, &mtn)) return -1;
+  {
+    Launch l(c, "xins_round", (double)x.NX * (40 + 8 * r.jumps));
+    HIPCHK(c, hipMemsetAsync(r.xf, 0xFF, (size_t)x.NX * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(r.hasb, 0, x.NX, c->stream));
+    hipLaunchKernelGGL(k_x2_xf, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb, r.d_only,
+                       x.xpar, r.p2A, r.xf);
+    hipLaunchKernelGGL(k_x2_anchor, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                       r.d_only, x.xpar, x.xk, r.xf, r.prevne, r.p2A, L.G, mt, mtn, round == 0 ? 1u : 0u, r.anc,
+                       x.ctl);
+    hipLaunchKernelGGL(k_x2_chain, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                       r.d_only, r.anc, r.jmp, r.hasb);
+    for (uint32_t j = 0; j < r.jumps; j++)
+      hipLaunchKernelGGL(k_x2_jump, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                         r.d_only, r.jmp);
+    hipLaunchKernelGGL(k_x2_build, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, L.d_sb,
+                       r.d_only, r.anc, r.jmp, r.hasb, L.spar, L.skd);
+  }
+  if (check_launch(c, "xins_round")) return -1;
+  const auto moving = [&](const XGroup &g) {
+    for (uint32_t f = 0; f < x.F; f++)
+      if (r.only[f] && L.plan.sb[f] >= g.base && L.plan.sb[f] < g.base + g.off.back()) return true;
+    return false;
+  };
+  if (x_weave_groups(x, L, moving)) return -1;
+  HIPCHK(c, hipMemsetAsync(r.moved, 0, x.F, c->stream));
+  if (x2_positions(x, r, 0, r.p2B, r.p2A)) return -1;
+  std::swap(r.p2A, r.p2B);
+  return 0;
+}
+
+// Phase 2: documents with an early node, anchor rounds on layout 2 from phase
+// 1's weave until the weave reproduces itself (the fold's, by induction over
+// the nodes in id order); a small document still moving after x_round_cap
+// rounds is folded serially instead.
+int x2_rounds(XCall &x) {
+  cw_ctx *c = x.c;
+  const uint32_t F = x.F;
+  XRounds r;
+  if (x2_setup(x, r)) return -1;
+  std::vector<uint8_t> h_moved(F);
+  for (uint32_t round = 0;; round++) {
+    if (x2_round(x, r, round)) return -1;
+    const uint32_t *pc = read_small(c, x.ctl, 8, NO_WAIT);
+    if (!pc) return -1;
+    HIPCHK(c, hipMemcpyAsync(h_moved.data(), r.moved, F, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
+    bool more = false;
+    for (uint32_t f = 0; f < F; f++) {
+      r.only[f] = r.only[f] && h_moved[f];  // a document that reproduced its weave is done
+      if (r.only[f] && round + 1 >= c->x_round_cap && x.xoff[f + 1] - x.xoff[f] <= X_CAP_FOLD_MAX) {
+        r.only[f] = 0;  // small and still moving: the serial fold (emitted after the synthetic lists)
+        x.run[f] = 1;
+        x.any_serial = true;
+      }
+      more |= r.only[f] != 0;
+    }
+    if (!more) return 0;
+    if (round > x.NX + 2) return fail(c, "exact path: no fixed point after %u rounds", round);
+    HIPCHK(c, hipMemcpy(r.d_only, r.only.data(), F, hipMemcpyHostToDevice));
+  }
+}
+
+// The converged layout-2 weaves back into layout 1 for the emission.
+int x2_compact(XCall &x) {
+  cw_ctx *c = x.c;
+  const dim3 GT(x.T), B256(256);
+  {
+    Launch l(c, "xsyn_compact", (double)x.NX * 16);
+    hipLaunchKernelGGL(k_x2_count, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, x.L2.d_sb,
+                       x.L2.wperm, x.tcnt);
+    hipLaunchKernelGGL(k_xapp_scan, dim3(1), dim3(1024), 0, c->stream, x.tcnt, x.T);
+    hipLaunchKernelGGL(k_x2_compact, GT, B256, 0, c->stream, x.tile_start, x.tile_doc, x.sub_off, x.L1.d_sb,
+                       x.L2.d_sb, x.tcnt, x.L2.wperm, x.L1.wperm, x.ctl);
+  }
+  return check_launch(c, "xsyn_compact");
+}
+
+// Layout 1's weaves into the caller's arrays at out_off (a document of the
+// rounds: a second pass for its render bits, hide? against the next node).
+int x_emit(XCall &x) {
+  cw_ctx *c = x.c;
+  const XLayout &L = x.L1;
+  const uint32_t *pc = read_small(c, x.ctl, 8);
+  if (!pc) return -1;
+  if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
+  hipLaunchKernelGGL(k_xsyn_zero, dim3((x.F + 63) / 64), dim3(64), 0, c->stream, L.d_sb, x.F, x.d_odoc,
+                     x.out->visible_count);
+  for (uint32_t adj = 0; adj < (x.any_x2 ? 2u : 1u); adj++) {
+    Launch l(c, "xsyn_emit", (double)x.NX * (4 + 4 + 4 + 1) + (double)x.NX / 8);
+    hipLaunchKernelGGL(k_xsyn_emit, dim3(x.T), dim3(256), 0, c->stream, x.tile_start, x.tile_doc, x.sub_off,
+                       L.d_sb, x.d_x2, adj, L.wperm, L.wbits, x.xk, x.xpar, x.sval, x.d_oof, x.d_odoc,
+                       x.out->weave_perm, x.out->visible_bits, x.out->visible_count);
+  }
+  return check_launch(c, "xsyn_emit");
+}
+
+// xfold: the literal fold, one lane a document, for the documents in run.
+int x_fold(XCall &x) {
+  cw_ctx *c = x.c;
+  if (x.any_serial) {
+    uint8_t *d_run = x_upload(c, "x_run", x.run);
+    uint32_t *xnext = scratch_t<uint32_t>(c, "x_next", x.NX);
+    if (!d_run || !xnext) return fail(c, "out of device memory (exact path)");
+    Launch l(c, "xfold", (double)x.NX * 22);
+    hipLaunchKernelGGL(k_xfold, dim3((x.F + 63) / 64), dim3(64), 0, c->stream, x.sub_off, x.F, x.xpar, x.xk,
+                       x.early, xnext, x.sval, x.d_oof, x.d_odoc, x.out->weave_perm, x.out->visible_bits,
+                       x.out->visible_count, d_run);
+  }
+  return check_launch(c, "xfold");
+}
+
 // The flagged documents after the join (xpar: cause rank / X_NIL / X_END by
 // rank, xk: kinds by rank, early: "has an older child" by rank, sval: input
 // index by rank or nullptr; dearly / dapp: per document "has an early node"
@@ -1266,327 +1633,48 @@ int exact_weave_flagged(cw_ctx *c, uint32_t F, const std::vector<uint64_t> &xoff
                         const uint32_t *xpar, const uint8_t *xk, const uint8_t *early,
                         const uint32_t *sval, const uint64_t *d_oof, const uint32_t *d_odoc,
                         const uint8_t *dearly, const uint32_t *dapp, cw_list_result *out) {
-  const uint32_t NX = (uint32_t)xoff.back();
-  if (ensure_tables(c, F, xoff.data())) return -1;
-  uint32_t *tile_start = dev_tab(c, "t_tile_start"), *tile_doc = dev_tab(c, "t_tile_doc"),
-           *sub_off = dev_tab(c, "t_doc_off");
-  const dim3 B256(256), GF((F + 63) / 64), B64(64);
-  const uint32_t T = c->tab.T;
-  std::vector<uint8_t> h_early(F), run(F, 0), x2(F, 0);
-  std::vector<uint32_t> h_app(F);
-  HIPCHK(c, hipMemcpyAsync(h_early.data(), dearly, F, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(h_app.data(), dapp, (size_t)F * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  // synthetic lists: documents without an early node, documents with one
-  // (phase 2 reweaves only those), then each giant document on its own
-  struct Group {
-    bool giant, early;
-    uint64_t base;  // first synthetic index (a multiple of 32: its bits start a word)
-    std::vector<uint64_t> off;
-  };
-  std::vector<Group> groups;
-  std::vector<uint32_t> sb(F, X_NONE);
-  uint64_t NS = 0, A = 0;
-  bool any_serial = false, any_x2 = false;
-  {
-    std::vector<uint32_t> small[2], big;
-    for (uint32_t f = 0; f < F; f++) {
-      const uint64_t n = xoff[f + 1] - xoff[f];
-      if (c->xfold && h_early[f] && n <= XFOLD_MAX) {  // xfold: the serial fold (cross-check)
-        run[f] = 1;
-        any_serial = true;
-        continue;
-      }
-      A += h_app[f];
-      x2[f] = h_early[f] ? 1 : 0;
-      any_x2 |= h_early[f] != 0;
-      if (n + 1 >= c->giant_min || n + 1 >= LINK_IDX) big.push_back(f);
-      else small[h_early[f] ? 1 : 0].push_back(f);
-    }
-    for (int e = 0; e < 2; e++) {
-      if (small[e].empty()) continue;
-      Group g{false, e == 1, NS, {0}};
-      for (uint32_t f : small[e]) {
-        sb[f] = (uint32_t)(NS + g.off.back());
-        g.off.push_back(g.off.back() + (xoff[f + 1] - xoff[f]) + 1);
-      }
-      NS = (NS + g.off.back() + 31) & ~31ull;
-      groups.push_back(std::move(g));
-    }
-    for (uint32_t f : big) {
-      const uint64_t n = xoff[f + 1] - xoff[f];
-      sb[f] = (uint32_t)NS;
-      groups.push_back(Group{true, h_early[f] != 0, NS, {0, n + 1}});
-      NS = (NS + n + 1 + 31) & ~31ull;
-    }
+  XCall x{c, F, xoff, xpar, xk, early, sval, d_oof, d_odoc, out, (uint32_t)xoff.back()};
+  if (x_tables(x) || x_plan_call(x, dearly, dapp)) return -1;
+  if (!x.L1.plan.groups.empty()) {
+    if (x_static(x) || x_resolve(x)) return -1;
+    if (x.any_x2 && (x2_rounds(x) || x2_compact(x))) return -1;
+    if (x_emit(x)) return -1;
   }
-  if (NS >= 0xFFFFFFF0ull - 16) return fail(c, "exact path: %llu synthetic nodes", (unsigned long long)NS);
-  c->x_iters = 0;
-  if (!groups.empty()) {
-    const uint64_t NP = ((NS + 15) & ~15ull) + 16;  // min-tree level 0, padded
-    uint32_t *d_sb = x_upload(c, "x_sbase", sb);
-    uint8_t *d_x2 = x_upload(c, "x_x2", x2);
-    uint32_t *spar = scratch_t<uint32_t>(c, "x_spar", NS), *wperm = scratch_t<uint32_t>(c, "x_wperm", NS);
-    uint8_t *skd = scratch_t<uint8_t>(c, "x_skd", NS);
-    uint32_t *wbits = scratch_t<uint32_t>(c, "x_wbits", NS / 32 + 1);
-    uint32_t *G = scratch_t<uint32_t>(c, "x_G", NP), *AUX = scratch_t<uint32_t>(c, "x_aux", NP);
-    uint32_t *posA = scratch_t<uint32_t>(c, "x_pos", NS), *ctop = scratch_t<uint32_t>(c, "x_ctop", NS);
-    uint32_t *Nof = scratch_t<uint32_t>(c, "x_nof", NS), *ctl = scratch_t<uint32_t>(c, "x_ctl", 2);
-    size_t gmax = 1;
-    for (auto &g : groups) gmax = std::max(gmax, g.off.size() - 1);
-    uint32_t *wvc = scratch_t<uint32_t>(c, "x_wvc", gmax), *wst = scratch_t<uint32_t>(c, "x_wst", gmax);
-    if (!d_sb || !d_x2 || !spar || !wperm || !skd || !wbits || !G || !AUX || !posA || !ctop || !Nof ||
-        !ctl || !wvc || !wst)
-      return fail(c, "out of device memory (exact path, %llu synthetic nodes)", (unsigned long long)NS);
-    HIPCHK(c, hipMemsetAsync(ctl, 0, 8, c->stream));
-    // weave the synthetic lists of every group (or only those with an early node)
-    auto weave_groups = [&](bool early_only) -> int {
-      for (auto &g : groups) {
-        if (early_only && !g.early) continue;
-        const uint64_t Dg = g.off.size() - 1, Ng = g.off.back();
-        if (ensure_tables(c, Dg, g.off.data(), g.giant)) return -1;
-        HIPCHK(c, hipMemsetAsync(wst, 0, Dg * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(wvc, 0, Dg * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(wbits + g.base / 32, 0, (Ng + 31) / 32 * 4, c->stream));
-        cw_list_result sr{};
-        sr.weave_perm = wperm + g.base;
-        sr.visible_bits = wbits + g.base / 32;
-        sr.visible_count = wvc;
-        sr.status = wst;
-        if (weave_tail(c, Dg, (uint32_t)Ng, g.giant, spar + g.base, skd + g.base, nullptr, nullptr,
-                       nullptr, 0, &sr))
-          return -1;
-        c->x_iters++;
-      }
-      if (ensure_tables(c, F, xoff.data())) return -1;  // the flagged documents' tiles again
-      tile_start = dev_tab(c, "t_tile_start");
-      tile_doc = dev_tab(c, "t_tile_doc");
-      sub_off = dev_tab(c, "t_doc_off");
-      return 0;
-    };
-    auto positions = [&](uint32_t mode, const uint8_t *only, uint32_t *pos, const uint32_t *posold) -> int {
-      HIPCHK(c, hipMemsetAsync(G, 0xFF, NP * 4, c->stream));
-      HIPCHK(c, hipMemsetAsync(AUX, 0xFF, NP * 4, c->stream));
-      Launch L(c, "xsyn_pos", (double)NX * 13);
-      hipLaunchKernelGGL(k_xs_pos, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb, only,
-                         wperm, skd, xk, mode, G, AUX, pos, posold, ctl);
-      return check_launch(c, "xsyn_pos");
-    };
-    // phase 1: the static forest, every appended node's T, the final weave
-    hipLaunchKernelGGL(k_xsyn_build, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb,
-                       xpar, xk, spar, skd);
-    if (check_launch(c, "xsyn_build")) return -1;
-    if (weave_groups(false)) return -1;
-    uint32_t *app_list = nullptr, *app_idx = nullptr;
-    if (A > 0) {
-      if (positions(0, nullptr, posA, nullptr)) return -1;
-      XMinTree mt, mtx;
-      if (mt_build(c, "x_mtG", G, NP, &mt) || mt_build(c, "x_mtA", AUX, NP, &mtx)) return -1;
-      app_list = scratch_t<uint32_t>(c, "x_app", A);
-      app_idx = scratch_t<uint32_t>(c, "x_appidx", NX);
-      uint32_t *app_doc = scratch_t<uint32_t>(c, "x_appdoc", A), *Tsyn = scratch_t<uint32_t>(c, "x_T", A);
-      uint32_t *tcnt = scratch_t<uint32_t>(c, "x_tcnt", T);
-      if (!app_list || !app_idx || !app_doc || !Tsyn || !tcnt)
-        return fail(c, "out of device memory (exact path, %llu appended nodes)", (unsigned long long)A);
-      const uint32_t A32 = (uint32_t)A;
-      {
-        Launch L(c, "xsyn_resolve", (double)NX * 16 + (double)A * 256);
-        hipLaunchKernelGGL(k_xctop, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb, spar,
-                           skd, ctop);
-        hipLaunchKernelGGL(k_xapp_count, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb,
-                           xpar, tcnt);
-        hipLaunchKernelGGL(k_xapp_scan, dim3(1), dim3(1024), 0, c->stream, tcnt, T);
-        hipLaunchKernelGGL(k_xapp_scatter, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off,
-                           d_sb, xpar, tcnt, app_list, app_doc, app_idx);
-        HIPCHK(c, hipMemsetAsync(Nof, 0xFF, NS * 4, c->stream));
-        hipLaunchKernelGGL(k_xres1, dim3((A32 + 255) / 256), B256, 0, c->stream, app_list, app_doc, A32,
-                           sub_off, d_sb, xk, posA, G, ctop, mt, Tsyn, Nof, ctl);
-        hipLaunchKernelGGL(k_xres2, dim3(A32), B64, 0, c->stream, app_list, app_doc, A32, sub_off, d_sb,
-                           xpar, xk, posA, G, ctop, mt, mtx, Tsyn, Nof, ctl);
-        hipLaunchKernelGGL(k_xsyn_final, dim3((A32 + 255) / 256), B256, 0, c->stream, app_list, app_doc,
-                           A32, sub_off, d_sb, xk, Tsyn, spar, skd);
-      }
-      if (check_launch(c, "xsyn_resolve")) return -1;
-      if (weave_groups(false)) return -1;
-    }
-    // phase 2: documents with an early node, anchor rounds on layout 2 from
-    // phase 1's weave until the weave reproduces itself (the fold's, by
-    // induction over the nodes in id order); a small document still moving
-    // after X_ROUND_CAP rounds is folded serially instead
-    if (any_x2) {
-      std::vector<uint32_t> sb2(F, X_NONE);
-      std::vector<Group> groups2;
-      uint64_t NS2 = 0;
-      uint32_t nmax = 1;
-      {
-        std::vector<uint32_t> small2, big2;
-        for (uint32_t f = 0; f < F; f++) {
-          if (!x2[f]) continue;
-          const uint64_t n = xoff[f + 1] - xoff[f];
-          nmax = std::max<uint32_t>(nmax, (uint32_t)n);
-          if (2 * n + 1 >= c->giant_min || 2 * n + 1 >= LINK_IDX) big2.push_back(f);
-          else small2.push_back(f);
-        }
-        if (!small2.empty()) {
-          Group g{false, true, NS2, {0}};
-          for (uint32_t f : small2) {
-            sb2[f] = (uint32_t)(NS2 + g.off.back());
-            g.off.push_back(g.off.back() + 2 * (xoff[f + 1] - xoff[f]) + 1);
-          }
-          NS2 = (NS2 + g.off.back() + 31) & ~31ull;
-          groups2.push_back(std::move(g));
-        }
-        for (uint32_t f : big2) {
-          const uint64_t n = xoff[f + 1] - xoff[f];
-          sb2[f] = (uint32_t)NS2;
-          groups2.push_back(Group{true, true, NS2, {0, 2 * n + 1}});
-          NS2 = (NS2 + 2 * n + 1 + 31) & ~31ull;
-        }
-      }
-      if (NS2 >= 0xFFFFFFF0ull - 16) return fail(c, "exact path: %llu layout-2 nodes", (unsigned long long)NS2);
-      const uint64_t NP2 = ((NS2 + 15) & ~15ull) + 16;
-      uint32_t *d_sb2 = x_upload(c, "x_sbase2", sb2);
-      uint8_t *d_only = x_upload(c, "x_only", x2);
-      uint32_t *spar2 = scratch_t<uint32_t>(c, "x_spar2", NS2), *wperm2 = scratch_t<uint32_t>(c, "x_wperm2", NS2);
-      uint8_t *skd2 = scratch_t<uint8_t>(c, "x_skd2", NS2);
-      uint32_t *wbits2 = scratch_t<uint32_t>(c, "x_wbits2", NS2 / 32 + 1);
-      uint32_t *G2 = scratch_t<uint32_t>(c, "x_G2", NP2), *AUX2 = scratch_t<uint32_t>(c, "x_aux2", NP2);
-      uint32_t *p2A = scratch_t<uint32_t>(c, "x_pos2A", NS2), *p2B = scratch_t<uint32_t>(c, "x_pos2B", NS2);
-      uint32_t *xf = scratch_t<uint32_t>(c, "x_xf", NX), *anc = scratch_t<uint32_t>(c, "x_anc", NX);
-      uint32_t *jmp = scratch_t<uint32_t>(c, "x_jmp", NX), *prevne = scratch_t<uint32_t>(c, "x_prevne", NX);
-      uint8_t *hasb = scratch_t<uint8_t>(c, "x_hasb", NX), *moved = scratch_t<uint8_t>(c, "x_moved", F);
-      size_t gmax2 = 1;
-      for (auto &g : groups2) gmax2 = std::max(gmax2, g.off.size() - 1);
-      uint32_t *wvc2 = scratch_t<uint32_t>(c, "x_wvc", std::max(gmax, gmax2)),
-               *wst2 = scratch_t<uint32_t>(c, "x_wst", std::max(gmax, gmax2));
-      if (!d_sb2 || !d_only || !spar2 || !wperm2 || !skd2 || !wbits2 || !G2 || !AUX2 || !p2A || !p2B || !xf ||
-          !anc || !jmp || !prevne || !hasb || !moved || !wvc2 || !wst2)
-        return fail(c, "out of device memory (exact path rounds, %llu layout-2 nodes)", (unsigned long long)NS2);
-      if (A > 0) {  // the previous non-early appended node of every appended node
-        const uint32_t A32 = (uint32_t)A, C = (A32 + 255) / 256;
-        uint32_t *cmax = scratch_t<uint32_t>(c, "x_necmax", C);
-        uint32_t *app_doc = scratch_t<uint32_t>(c, "x_appdoc", A);
-        if (!cmax || !app_doc) return fail(c, "out of device memory (exact path rounds)");
-        Launch L(c, "xins_prevne", (double)A * 14);
-        hipLaunchKernelGGL(k_x2_ne_chunk, dim3(C), B256, 0, c->stream, app_list, A32, early, cmax);
-        hipLaunchKernelGGL(k_x2_ne_scan, dim3(1), dim3(1024), 0, c->stream, cmax, C);
-        hipLaunchKernelGGL(k_x2_ne_final, dim3(C), B256, 0, c->stream, app_list, app_doc, A32, early, cmax,
-                           prevne);
-      }
-      if (check_launch(c, "xins_prevne")) return -1;
-      auto positions2 = [&](uint32_t from1, uint32_t *pos, const uint32_t *posold) -> int {
-        HIPCHK(c, hipMemsetAsync(G2, 0xFF, NP2 * 4, c->stream));
-        HIPCHK(c, hipMemsetAsync(AUX2, 0xFF, NP2 * 4, c->stream));
-        Launch L(c, "xsyn_pos", (double)NX * 26);
-        hipLaunchKernelGGL(k_x2_pos, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb, d_sb2,
-                           d_only, from1, wperm, wperm2, xk, G2, AUX2, pos, posold, moved, ctl);
-        return check_launch(c, "xsyn_pos");
-      };
-      if (positions2(1, p2A, nullptr)) return -1;
-      // launches of k_x2_jump: reach (X2_JUMPS + 1)^launches >= nmax
-      uint32_t jumps = 1;
-      for (uint64_t reach = 1; reach < nmax; reach *= X2_JUMPS + 1) jumps++;
-      std::vector<uint8_t> only(x2), h_moved(F);
-      for (uint32_t round = 0;; round++) {
-        XMinTree mt, mtn;
-        if (mt_build(c, "x_mtG", G2, NP2, &mt) || mt_build(c, "x_mtA", AUX2, NP2, &mtn)) return -1;
-        {
-          Launch L(c, "xins_round", (double)NX * (40 + 8 * jumps));
-          HIPCHK(c, hipMemsetAsync(xf, 0xFF, (size_t)NX * 4, c->stream));
-          HIPCHK(c, hipMemsetAsync(hasb, 0, NX, c->stream));
-          hipLaunchKernelGGL(k_x2_xf, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2, d_only,
-                             xpar, p2A, xf);
-          hipLaunchKernelGGL(k_x2_anchor, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2,
-                             d_only, xpar, xk, xf, prevne, p2A, G2, mt, mtn, round == 0 ? 1u : 0u, anc, ctl);
-          hipLaunchKernelGGL(k_x2_chain, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2,
-                             d_only, anc, jmp, hasb);
-          for (uint32_t j = 0; j < jumps; j++)
-            hipLaunchKernelGGL(k_x2_jump, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2,
-                               d_only, jmp);
-          hipLaunchKernelGGL(k_x2_build, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2,
-                             d_only, anc, jmp, hasb, spar2, skd2);
-        }
-        if (check_launch(c, "xins_round")) return -1;
-        // weave the layout-2 groups that hold a moving document
-        for (auto &g : groups2) {
-          bool any = false;
-          for (uint32_t f = 0; f < F && !any; f++)
-            any = only[f] && sb2[f] >= g.base && sb2[f] < g.base + g.off.back();
-          if (!any) continue;
-          const uint64_t Dg = g.off.size() - 1, Ng = g.off.back();
-          if (ensure_tables(c, Dg, g.off.data(), g.giant)) return -1;
-          HIPCHK(c, hipMemsetAsync(wst2, 0, Dg * 4, c->stream));
-          HIPCHK(c, hipMemsetAsync(wvc2, 0, Dg * 4, c->stream));
-          cw_list_result sr{};
-          sr.weave_perm = wperm2 + g.base;
-          sr.visible_bits = wbits2 + g.base / 32;
-          sr.visible_count = wvc2;
-          sr.status = wst2;
-          if (weave_tail(c, Dg, (uint32_t)Ng, g.giant, spar2 + g.base, skd2 + g.base, nullptr, nullptr,
-                         nullptr, 0, &sr))
-            return -1;
-          c->x_iters++;
-        }
-        if (ensure_tables(c, F, xoff.data())) return -1;
-        tile_start = dev_tab(c, "t_tile_start");
-        tile_doc = dev_tab(c, "t_tile_doc");
-        sub_off = dev_tab(c, "t_doc_off");
-        HIPCHK(c, hipMemsetAsync(moved, 0, F, c->stream));
-        if (positions2(0, p2B, p2A)) return -1;
-        std::swap(p2A, p2B);
-        const uint32_t *pc = read_small(c, ctl, 8, NO_WAIT);
-        if (!pc) return -1;
-        HIPCHK(c, hipMemcpyAsync(h_moved.data(), moved, F, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
-        bool more = false;
-        for (uint32_t f = 0; f < F; f++) {
-          only[f] = only[f] && h_moved[f];  // a document that reproduced its weave is done
-          if (only[f] && round + 1 >= c->x_round_cap && xoff[f + 1] - xoff[f] <= X_CAP_FOLD_MAX) {
-            only[f] = 0;  // small and still moving: the serial fold (emitted after the synthetic lists)
-            run[f] = 1;
-            any_serial = true;
-          }
-          more |= only[f] != 0;
-        }
-        if (!more) break;
-        if (round > NX + 2) return fail(c, "exact path: no fixed point after %u rounds", round);
-        HIPCHK(c, hipMemcpy(d_only, only.data(), F, hipMemcpyHostToDevice));
-      }
-      // the converged layout-2 weaves back into layout 1 for the emission
-      uint32_t *tcnt2 = scratch_t<uint32_t>(c, "x_tcnt", T);
-      if (!tcnt2) return fail(c, "out of device memory (exact path)");
-      {
-        Launch L(c, "xsyn_compact", (double)NX * 16);
-        hipLaunchKernelGGL(k_x2_count, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb2, wperm2,
-                           tcnt2);
-        hipLaunchKernelGGL(k_xapp_scan, dim3(1), dim3(1024), 0, c->stream, tcnt2, T);
-        hipLaunchKernelGGL(k_x2_compact, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb,
-                           d_sb2, tcnt2, wperm2, wperm, ctl);
-      }
-      if (check_launch(c, "xsyn_compact")) return -1;
-    }
-    const uint32_t *pc = read_small(c, ctl, 8);
-    if (!pc) return -1;
-    if (pc[1]) return fail(c, "exact path: inconsistent synthetic weave (%u)", pc[1]);
-    hipLaunchKernelGGL(k_xsyn_zero, GF, B64, 0, c->stream, d_sb, F, d_odoc, out->visible_count);
-    for (uint32_t adj = 0; adj < (any_x2 ? 2u : 1u); adj++) {
-      Launch L(c, "xsyn_emit", (double)NX * (4 + 4 + 4 + 1) + (double)NX / 8);
-      hipLaunchKernelGGL(k_xsyn_emit, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_sb, d_x2,
-                         adj, wperm, wbits, xk, xpar, sval, d_oof, d_odoc, out->weave_perm,
-                         out->visible_bits, out->visible_count);
-    }
-    if (check_launch(c, "xsyn_emit")) return -1;
-  }
-  if (any_serial) {  // xfold: the literal fold, one lane a document
-    uint8_t *d_run = x_upload(c, "x_run", run);
-    uint32_t *xnext = scratch_t<uint32_t>(c, "x_next", NX);
-    if (!d_run || !xnext) return fail(c, "out of device memory (exact path)");
-    Launch L(c, "xfold", (double)NX * 22);
-    hipLaunchKernelGGL(k_xfold, GF, B64, 0, c->stream, sub_off, F, xpar, xk, early, xnext, sval,
-                       d_oof, d_odoc, out->weave_perm, out->visible_bits, out->visible_count, d_run);
-  }
-  return check_launch(c, "xfold");
+  return x_fold(x);
+}
+
+// One document's per-document buffers (odoc = 0, oof = 0) and its flags,
+// cleared for the join; *xk: kinds by rank, when they are not the caller's.
+struct XOne {
+  uint32_t *xpar, *dorph, *odoc;
+  uint8_t *early, *dearly;
+  uint64_t *oof;
+};
+int x_one_doc(cw_ctx *c, uint32_t n, XOne *o, uint8_t **xk = nullptr) {
+  if (xk) *xk = scratch_t<uint8_t>(c, "x_k", n);
+  o->xpar = scratch_t<uint32_t>(c, "x_par", n), o->dorph = scratch_t<uint32_t>(c, "x_dorph", 1);
+  o->early = scratch_t<uint8_t>(c, "x_early", n), o->dearly = scratch_t<uint8_t>(c, "x_dearly", 1);
+  o->odoc = scratch_t<uint32_t>(c, "x_rodoc", 1);
+  o->oof = scratch_t<uint64_t>(c, "x_roof", 1);
+  if ((xk && !*xk) || !o->xpar || !o->dorph || !o->early || !o->dearly || !o->odoc || !o->oof)
+    return fail(c, "out of device memory (exact path, %u nodes)", n);
+  HIPCHK(c, hipMemsetAsync(o->odoc, 0, 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(o->oof, 0, 8, c->stream));
+  HIPCHK(c, hipMemsetAsync(o->early, 0, n, c->stream));
+  HIPCHK(c, hipMemsetAsync(o->dearly, 0, 1, c->stream));
+  HIPCHK(c, hipMemsetAsync(o->dorph, 0, 4, c->stream));
+  return 0;
+}
+
+// spin: the id order (skey, sval) partitioned by site; *yv = the input indices
+// in yarn order.  (ykA, yvA), (ykB, "x_yv") are the sort's ping-pong buffers.
+int x_yarn_sort(cw_ctx *c, const cw_list_batch *bt, const uint64_t *skey, const uint32_t *sval,
+                uint64_t *ykA, uint32_t *yvA, uint64_t *ykB, uint32_t n, uint32_t **yv) {
+  uint32_t *yvB = scratch_t<uint32_t>(c, "x_yv", n);
+  if (!ykA || !yvA || !ykB || !yvB) return fail(c, "out of device memory (exact path yarns)");
+  uint64_t *yk;
+  return radix_sort<uint64_t>(c, "xyarns", skey, sval, ykA, yvA, ykB, yvB, bt->site_bits, bt->site_shift, n,
+                              &yk, yv);
 }
 
 // exact_fixup for one giant list whose front end left its sorted ids and rank
@@ -1597,54 +1685,47 @@ int exact_giant_front(cw_ctx *c, const cw_list_batch *bt, cw_list_result *out) {
   const uint32_t N = xf.n;
   const std::vector<uint64_t> xoff = {0, N};
   if (ensure_tables(c, 1, xoff.data())) return -1;
-  uint8_t *xk = scratch_t<uint8_t>(c, "x_k", N), *early = scratch_t<uint8_t>(c, "x_early", N);
-  uint8_t *dearly = scratch_t<uint8_t>(c, "x_dearly", 1);
-  uint32_t *dorph = scratch_t<uint32_t>(c, "x_dorph", 1), *xpar = scratch_t<uint32_t>(c, "x_par", N);
-  uint32_t *odoc = scratch_t<uint32_t>(c, "x_rodoc", 1);
-  uint64_t *oof = scratch_t<uint64_t>(c, "x_roof", 1);
-  if (!xk || !early || !dearly || !dorph || !xpar || !odoc || !oof)
-    return fail(c, "out of device memory (exact path, %u nodes)", N);
-  HIPCHK(c, hipMemsetAsync(odoc, 0, 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(oof, 0, 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(early, 0, N, c->stream));
-  HIPCHK(c, hipMemsetAsync(dearly, 0, 1, c->stream));
-  HIPCHK(c, hipMemsetAsync(dorph, 0, 4, c->stream));
+  XOne o;
+  uint8_t *xk;
+  if (x_one_doc(c, N, &o, &xk)) return -1;
   {
     Launch L(c, "xjoin", (double)N * (4 + 8 + 4 + 1) + (double)N * 64);
     hipLaunchKernelGGL(k_xjoin_dir, dim3((N + 255) / 256), dim3(256), 0, c->stream, xf.skey, xf.sval,
-                       bt->cause_key, bt->kind, xf.ckk, N, xf.dir, xf.E, xpar, xk, early, dearly, dorph);
+                       bt->cause_key, bt->kind, xf.ckk, N, xf.dir, xf.E, o.xpar, xk, o.early, o.dearly,
+                       o.dorph);
   }
   if (check_launch(c, "xjoin")) return -1;
   if (out->max_ts) {
     hipLaunchKernelGGL(k_xmaxts, dim3(1), dim3(64), 0, c->stream, dev_tab(c, "t_doc_off"), 1u, xf.skey,
-                       bt->ts_shift, odoc, out->max_ts);
+                       bt->ts_shift, o.odoc, out->max_ts);
     if (check_launch(c, "xmaxts")) return -1;
   }
-  if (out->yarn_perm && bt->site_bits) {  // spin: the id order partitioned by site
-    uint64_t *ykA = scratch_t<uint64_t>(c, "x_skA", N), *ykB = scratch_t<uint64_t>(c, "x_skB", N);
-    uint32_t *yvA = scratch_t<uint32_t>(c, "x_svA", N), *yvB = scratch_t<uint32_t>(c, "x_yv", N);
-    if (!ykA || !ykB || !yvA || !yvB) return fail(c, "out of device memory (exact path yarns)");
-    uint64_t *yk;
+  if (out->yarn_perm && bt->site_bits) {
     uint32_t *yv;
-    if (radix_sort<uint64_t>(c, "xyarns", xf.skey, xf.sval, ykA, yvA, ykB, yvB, bt->site_bits,
-                             bt->site_shift, N, &yk, &yv))
+    if (x_yarn_sort(c, bt, xf.skey, xf.sval, scratch_t<uint64_t>(c, "x_skA", N),
+                    scratch_t<uint32_t>(c, "x_svA", N), scratch_t<uint64_t>(c, "x_skB", N), N, &yv))
       return -1;
     HIPCHK(c, hipMemcpyAsync(out->yarn_perm, yv, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
   }
-  return exact_weave_flagged(c, 1, xoff, xpar, xk, early, xf.sval, oof, odoc, dearly, dorph, out);
+  return exact_weave_flagged(c, 1, xoff, o.xpar, xk, o.early, xf.sval, o.oof, o.odoc, o.dearly, o.dorph, out);
 }
 
-// After the fast path has woven a batch (device arrays id/cause/kind laid out
-// by bt->doc_offsets, results in `out`): reweave its flagged documents by the
-// literal fold and overwrite their weave_perm, rendered bits and count, and
-// (when asked for) ::lamport-ts and yarns.  Status bits stay: they say the
-// document is one the reference's s/insert would have refused.  `hint` = 0
-// when the front end reported no flagged document (no readback needed).
-int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const uint64_t *cause,
-                const uint8_t *kind, cw_list_result *out, bool hint) {
+// The flagged documents of a batch: their first nodes in the batch (src),
+// their numbers (odoc) and their offsets in the compact batch (xoff).
+struct XDocs {
+  std::vector<uint64_t> xoff = std::vector<uint64_t>(1, 0), src;
+  std::vector<uint32_t> odoc;
+};
+constexpr int X_DOCS_NONE = 0, X_DOCS_LISTED = 1, X_DOCS_FRONT = 2;
+
+// Which documents the exact path takes, by the cheapest readback: one giant
+// list's status word copied out after its front end (X_DOCS_FRONT: that front
+// end also left what exact_giant_front needs), a few documents' words in one
+// small readback, or a count on the device before all words are read.
+// X_DOCS_*, or -1 after fail().
+int x_which_docs(cw_ctx *c, const cw_list_batch *bt, const cw_list_result *out, XDocs *docs) {
   const uint64_t D = bt->n_docs;
   const uint64_t *off = bt->doc_offsets;
-  if (!hint || D == 0 || off[D] == 0) return 0;
   constexpr uint64_t FEW_DOCS = 16;  // their status words fit the small readback
   static_assert(FEW_DOCS * 4 <= PIN_SMALL_BYTES, "exact_fixup: FEW_DOCS status words in one read_small");
   if (D == 1 && c->x_pending && bt->key_bits && bt->key_bits < 64) {
@@ -1652,8 +1733,8 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
     // set later, needs key_bits >= 64); wait for that copy, not for the stream
     HIPCHK(c, hipEventSynchronize(c->ev_status));
     const uint32_t st = c->pin_status[0];
-    if (!(st & X_MASK) || (st & X_SKIP)) return 0;
-    if (c->xfront.ok && c->xfront.n == off[1]) return exact_giant_front(c, bt, out);
+    if (!(st & X_MASK) || (st & X_SKIP)) return X_DOCS_NONE;
+    if (c->xfront.ok && c->xfront.n == off[1]) return X_DOCS_FRONT;
   } else if (D <= FEW_DOCS) {
     // a few documents: their status words in one readback
     const uint32_t *st = read_small(c, out->status, D * 4);
@@ -1661,7 +1742,7 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
     bool any = false;
     for (uint64_t d = 0; d < D; d++)
       any |= (st[d] & X_MASK) && !(st[d] & X_SKIP) && off[d + 1] > off[d];
-    if (!any) return 0;
+    if (!any) return X_DOCS_NONE;
   }
   uint32_t *cnt = scratch_t<uint32_t>(c, "x_cnt", 1);
   uint32_t *doff = scratch_t<uint32_t>(c, "x_doff", D + 1);
@@ -1678,111 +1759,128 @@ int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const ui
   if (check_launch(c, "xcount")) return -1;
   const uint32_t *pcnt = read_small(c, cnt, 4);
   if (!pcnt) return -1;
-  if (pcnt[0] == 0) return 0;
-  // which documents
+  if (pcnt[0] == 0) return X_DOCS_NONE;
   std::vector<uint32_t> st(D);
   HIPCHK(c, hipMemcpy(st.data(), out->status, D * 4, hipMemcpyDeviceToHost));
-  std::vector<uint64_t> xoff(1, 0), src;
-  std::vector<uint32_t> odoc;
   for (uint64_t d = 0; d < D; d++) {
     if (!(st[d] & X_MASK) || (st[d] & X_SKIP) || off[d + 1] == off[d]) continue;
-    src.push_back(off[d]);
-    odoc.push_back((uint32_t)d);
-    xoff.push_back(xoff.back() + (off[d + 1] - off[d]));
+    docs->src.push_back(off[d]);
+    docs->odoc.push_back((uint32_t)d);
+    docs->xoff.push_back(docs->xoff.back() + (off[d + 1] - off[d]));
   }
-  const uint32_t F = (uint32_t)odoc.size(), NX = (uint32_t)xoff.back();
-  if (ensure_tables(c, F, xoff.data())) return -1;
-  uint64_t *d_src = x_upload(c, "x_src", src);
-  uint32_t *d_odoc = x_upload(c, "x_odoc", odoc);
-  // (names of their own: the synthetic lists below run the list pipeline's tail)
-  uint64_t *xid = scratch_t<uint64_t>(c, "x_id", NX), *xca = scratch_t<uint64_t>(c, "x_cause", NX);
-  uint8_t *xkd = scratch_t<uint8_t>(c, "x_kind", NX), *xk = scratch_t<uint8_t>(c, "x_k", NX);
-  uint8_t *early = scratch_t<uint8_t>(c, "x_early", NX), *dearly = scratch_t<uint8_t>(c, "x_dearly", F);
-  uint32_t *dorph = scratch_t<uint32_t>(c, "x_dorph", F);
-  uint64_t *skA = scratch_t<uint64_t>(c, "x_skA", NX), *skB = scratch_t<uint64_t>(c, "x_skB", NX);
-  uint32_t *svA = scratch_t<uint32_t>(c, "x_svA", NX), *svB = scratch_t<uint32_t>(c, "x_svB", NX);
-  uint32_t *xpar = scratch_t<uint32_t>(c, "x_par", NX);
-  if (!d_src || !d_odoc || !xid || !xca || !xkd || !xk || !early || !dearly || !dorph || !skA || !skB ||
-      !svA || !svB || !xpar)
+  return X_DOCS_LISTED;
+}
+
+// The flagged documents as a compact batch, in id order and joined: what
+// exact_weave_flagged takes, and the sort's buffers for the yarns.
+struct XJoined {
+  uint32_t F, NX;
+  uint32_t *d_odoc, *xpar, *dorph, *sval;
+  uint64_t *d_oof, *xid, *skey;
+  uint8_t *xk, *early, *dearly;
+  uint64_t *skA, *skB;  // the id sort's ping-pong buffers: skey and sval lie in one of each
+  uint32_t *svA, *svB;
+};
+
+int x_gather_join(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const uint64_t *cause,
+                  const uint8_t *kind, const XDocs &docs, XJoined *j) {
+  const uint32_t F = j->F = (uint32_t)docs.odoc.size(), NX = j->NX = (uint32_t)docs.xoff.back();
+  if (ensure_tables(c, F, docs.xoff.data())) return -1;
+  uint64_t *d_src = x_upload(c, "x_src", docs.src);
+  j->d_odoc = x_upload(c, "x_odoc", docs.odoc);
+  // (names of their own: the synthetic lists run the list pipeline's tail)
+  j->xid = scratch_t<uint64_t>(c, "x_id", NX);
+  uint64_t *xca = scratch_t<uint64_t>(c, "x_cause", NX);
+  uint8_t *xkd = scratch_t<uint8_t>(c, "x_kind", NX);
+  j->xk = scratch_t<uint8_t>(c, "x_k", NX);
+  j->early = scratch_t<uint8_t>(c, "x_early", NX), j->dearly = scratch_t<uint8_t>(c, "x_dearly", F);
+  j->dorph = scratch_t<uint32_t>(c, "x_dorph", F);
+  j->skA = scratch_t<uint64_t>(c, "x_skA", NX), j->skB = scratch_t<uint64_t>(c, "x_skB", NX);
+  j->svA = scratch_t<uint32_t>(c, "x_svA", NX), j->svB = scratch_t<uint32_t>(c, "x_svB", NX);
+  j->xpar = scratch_t<uint32_t>(c, "x_par", NX);
+  if (!d_src || !j->d_odoc || !j->xid || !xca || !xkd || !j->xk || !j->early || !j->dearly || !j->dorph ||
+      !j->skA || !j->skB || !j->svA || !j->svB || !j->xpar)
     return fail(c, "out of device memory (exact path, %u nodes)", NX);
   uint32_t *tile_start = dev_tab(c, "t_tile_start"), *tile_doc = dev_tab(c, "t_tile_doc"),
            *sub_off = dev_tab(c, "t_doc_off");
-  const dim3 B256(256), GF((F + 63) / 64), B64(64);
-  const uint32_t T = c->tab.T;
+  const dim3 GT(c->tab.T), B256(256);
   {
     Launch L(c, "xgather", (double)NX * 34);
-    hipLaunchKernelGGL(k_xgather, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_src, id,
-                       cause, kind, xid, xca, xkd);
+    hipLaunchKernelGGL(k_xgather, GT, B256, 0, c->stream, tile_start, tile_doc, sub_off, d_src, id, cause,
+                       kind, j->xid, xca, xkd);
   }
   if (check_launch(c, "xgather")) return -1;
   uint32_t key_bits = bt->key_bits;
-  if (key_bits == 0 && find_key_bits(c, xid, NX, &key_bits)) return -1;
+  if (key_bits == 0 && find_key_bits(c, j->xid, NX, &key_bits)) return -1;
   if (key_bits > 64) key_bits = 64;
-  uint64_t *skey;
-  uint32_t *sval;
-  if (radix_sort<uint64_t>(c, "xsort", xid, nullptr, skA, svA, skB, svB, key_bits, 0, NX, &skey,
-                           &sval))
+  if (radix_sort<uint64_t>(c, "xsort", j->xid, nullptr, j->skA, j->svA, j->skB, j->svB, key_bits, 0, NX,
+                           &j->skey, &j->sval))
     return -1;
-  HIPCHK(c, hipMemsetAsync(early, 0, NX, c->stream));
-  HIPCHK(c, hipMemsetAsync(dearly, 0, F, c->stream));
-  HIPCHK(c, hipMemsetAsync(dorph, 0, (size_t)F * 4, c->stream));
+  HIPCHK(c, hipMemsetAsync(j->early, 0, NX, c->stream));
+  HIPCHK(c, hipMemsetAsync(j->dearly, 0, F, c->stream));
+  HIPCHK(c, hipMemsetAsync(j->dorph, 0, (size_t)F * 4, c->stream));
   {
     Launch L(c, "xjoin", (double)NX * 30);
-    hipLaunchKernelGGL(k_xjoin, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, skey, sval,
-                       xca, xkd, xpar, xk, early, dearly, dorph);
+    hipLaunchKernelGGL(k_xjoin, GT, B256, 0, c->stream, tile_start, tile_doc, sub_off, j->skey, j->sval, xca,
+                       xkd, j->xpar, j->xk, j->early, j->dearly, j->dorph);
   }
   if (check_launch(c, "xjoin")) return -1;
-  uint64_t *d_oof;
-  {
-    std::vector<uint64_t> oof(F);
-    for (uint32_t f = 0; f < F; f++) oof[f] = src[f];
-    d_oof = x_upload(c, "x_oof", oof);
-    if (!d_oof) return fail(c, "out of device memory (exact path)");
-  }
-  // ::lamport-ts and the yarns (spin 1-arity: the id order partitioned by
-  // site) do not depend on the weave
+  j->d_oof = x_upload(c, "x_oof", docs.src);  // a document's outputs lie where its nodes do
+  if (!j->d_oof) return fail(c, "out of device memory (exact path)");
+  return 0;
+}
+
+// ::lamport-ts and the yarns (spin 1-arity: the id order partitioned by site)
+// do not depend on the weave.
+int x_ts_yarns(cw_ctx *c, const cw_list_batch *bt, const XJoined &j, cw_list_result *out) {
+  uint32_t *sub_off = dev_tab(c, "t_doc_off");
   if (out->max_ts) {
-    hipLaunchKernelGGL(k_xmaxts, GF, B64, 0, c->stream, sub_off, F, skey, bt->ts_shift, d_odoc,
-                       out->max_ts);
+    hipLaunchKernelGGL(k_xmaxts, dim3((j.F + 63) / 64), dim3(64), 0, c->stream, sub_off, j.F, j.skey,
+                       bt->ts_shift, j.d_odoc, out->max_ts);
     if (check_launch(c, "xmaxts")) return -1;
   }
   if (out->yarn_perm && bt->site_bits) {
-    uint64_t *ykA = skey == skA ? skB : skA;
-    uint32_t *yvA = sval == svA ? svB : svA;
-    uint32_t *yvB = scratch_t<uint32_t>(c, "x_yv", NX);
-    if (!yvB) return fail(c, "out of device memory (exact path yarns)");
-    uint64_t *yk;
-    uint32_t *yv;
-    if (radix_sort<uint64_t>(c, "xyarns", skey, sval, ykA, yvA, xid, yvB, bt->site_bits,
-                             bt->site_shift, NX, &yk, &yv))
+    uint32_t *yv;  // the sort's idle halves and the gathered ids (read no more) are its buffers
+    if (x_yarn_sort(c, bt, j.skey, j.sval, j.skey == j.skA ? j.skB : j.skA, j.sval == j.svA ? j.svB : j.svA,
+                    j.xid, j.NX, &yv))
       return -1;
-    hipLaunchKernelGGL(k_xscatter, dim3(T), B256, 0, c->stream, tile_start, tile_doc, sub_off, d_oof, yv,
-                       out->yarn_perm);
+    hipLaunchKernelGGL(k_xscatter, dim3(c->tab.T), dim3(256), 0, c->stream, dev_tab(c, "t_tile_start"),
+                       dev_tab(c, "t_tile_doc"), sub_off, j.d_oof, yv, out->yarn_perm);
     if (check_launch(c, "xscatter")) return -1;
   }
-  return exact_weave_flagged(c, F, xoff, xpar, xk, early, sval, d_oof, d_odoc, dearly, dorph, out);
+  return 0;
+}
+
+// After the fast path has woven a batch (device arrays id/cause/kind laid out
+// by bt->doc_offsets, results in `out`): reweave its flagged documents by the
+// literal fold and overwrite their weave_perm, rendered bits and count, and
+// (when asked for) ::lamport-ts and yarns.  Status bits stay: they say the
+// document is one the reference's s/insert would have refused.  `hint` = 0
+// when the front end reported no flagged document (no readback needed).
+int exact_fixup(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id, const uint64_t *cause,
+                const uint8_t *kind, cw_list_result *out, bool hint) {
+  if (!hint || bt->n_docs == 0 || bt->doc_offsets[bt->n_docs] == 0) return 0;
+  XDocs docs;
+  const int which = x_which_docs(c, bt, out, &docs);
+  if (which == X_DOCS_FRONT) return exact_giant_front(c, bt, out);
+  if (which != X_DOCS_LISTED) return which;
+  XJoined j;
+  if (x_gather_join(c, bt, id, cause, kind, docs, &j) || x_ts_yarns(c, bt, j, out)) return -1;
+  return exact_weave_flagged(c, j.F, docs.xoff, j.xpar, j.xk, j.early, j.sval, j.d_oof, j.d_odoc, j.dearly,
+                             j.dorph, out);
 }
 
 // cw_weave_ranked's exact path: the one list given by (par, kind) in rank order
 // (the same path as exact_fixup's documents).
 int exact_ranked(cw_ctx *c, const cw_ranked_list *l, cw_list_result *out) {
   const uint32_t n = (uint32_t)l->n;
-  uint32_t *xpar = scratch_t<uint32_t>(c, "x_par", n), *dorph = scratch_t<uint32_t>(c, "x_dorph", 1);
-  uint8_t *early = scratch_t<uint8_t>(c, "x_early", n), *dearly = scratch_t<uint8_t>(c, "x_dearly", 1);
-  uint32_t *odoc = scratch_t<uint32_t>(c, "x_rodoc", 1);
-  uint64_t *oof = scratch_t<uint64_t>(c, "x_roof", 1);
-  if (!xpar || !dorph || !early || !dearly || !odoc || !oof)
-    return fail(c, "out of device memory (exact path, %u nodes)", n);
-  HIPCHK(c, hipMemsetAsync(odoc, 0, 4, c->stream));
-  HIPCHK(c, hipMemsetAsync(oof, 0, 8, c->stream));
-  HIPCHK(c, hipMemsetAsync(early, 0, n, c->stream));
-  HIPCHK(c, hipMemsetAsync(dearly, 0, 1, c->stream));
-  HIPCHK(c, hipMemsetAsync(dorph, 0, 4, c->stream));
+  XOne o;
+  if (x_one_doc(c, n, &o)) return -1;
   hipLaunchKernelGGL(k_xranked_prep, dim3((n + 255) / 256), dim3(256), 0, c->stream, l->par, l->kind,
-                     n, xpar, early, dearly, dorph);
+                     n, o.xpar, o.early, o.dearly, o.dorph);
   if (check_launch(c, "xranked_prep")) return -1;
   const std::vector<uint64_t> xoff = {0, n};
-  return exact_weave_flagged(c, 1, xoff, xpar, l->kind, early, l->val, oof, odoc, dearly, dorph, out);
+  return exact_weave_flagged(c, 1, xoff, o.xpar, l->kind, o.early, l->val, o.oof, o.odoc, o.dearly, o.dorph, out);
 }
 
 }  // namespace

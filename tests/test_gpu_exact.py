@@ -364,6 +364,100 @@ def test_round_cap_hands_still_moving_documents_to_the_serial_fold():
     assert res.status[2] == 0
 
 
+def _every_group_docs():
+    """Model documents that, with giant_min = 4096, fill every kind of group of
+    both synthetic layouts (n + 1 slots a document in layout 1, 2n + 1 in
+    layout 2, a document of >= 4,096 slots in a group of its own):
+      0  600 nodes, clean: not flagged
+      1  900 nodes, absent causes: layout 1's group without an early node
+      2  1,200 nodes, absent and non-Lamport causes: the small group of both layouts
+      3  a reverse chain of 2,600 nodes: small in layout 1 (2,601 < 4,096),
+         its own group in layout 2 (5,201)
+      4  4,500 nodes, absent causes: its own group in layout 1, not in layout 2
+      5  a reverse chain of 4,500 nodes: its own group in both, and too large
+         for the serial fold after the round cap
+      6  two nodes, the second an orphan."""
+    from tests import exact_model as M
+
+    def broken(seed, n, orphans, non_lamport):
+        rng = random.Random(seed)
+        par, cls = M.random_doc(rng, n)
+        for r in rng.sample(range(1, n - 1), orphans + non_lamport):
+            par[r] = M.END if orphans > 0 else rng.randrange(r + 1, n)
+            orphans -= 1
+        return par, cls
+
+    return [M.random_doc(random.Random(51), 600), broken(52, 900, 25, 0), broken(53, 1200, 20, 12),
+            M.chain_doc("reverse", 2600, random.Random(54)), broken(55, 4500, 40, 0),
+            M.chain_doc("reverse", 4500, random.Random(56)), ([M.NIL, M.END], [0, 0])]
+
+
+def _every_group_run(options):
+    """The batch of _every_group_docs on a context with giant_min = 4096 and
+    the given options: (result, kernel_stats), bit-exact against the literal
+    fold."""
+    off, idk, ck, kd, lay = _rank_docs(_every_group_docs())
+    with abi.Weaver(0, options=dict(options, giant_min=4096)) as w:
+        w.reset_kernel_stats()
+        w.set_profiling(True)
+        res = check_batch(w, off, idk, ck, kd, lay, method=oracle.METHOD_LITERAL)
+        w.set_profiling(False)
+        stats = w.kernel_stats()
+    assert not res.status[0] and res.status[[1, 2, 4, 6]].all()
+    assert (res.status[[2, 3, 5]] & abi.STATUS_NON_LAMPORT).all()
+    return res, stats
+
+
+def test_every_kind_of_group_in_one_batch():
+    """Both synthetic layouts with every kind of group at once (small documents
+    without and with an early node, documents in a group of their own in
+    layout 1, in layout 2, in both): bit-exact, some group on the giant tree,
+    the rounds within 2 log2 n + 4, no serial fold.  With x_round_cap = 1 the
+    small documents still moving after the first round take the serial fold
+    and the 4,500-node chain (above X_CAP_FOLD_MAX) stays in the rounds."""
+    import math
+
+    _, stats = _every_group_run({})
+    assert "geff" in stats and ("tour" in stats or "tree" in stats), sorted(stats)
+    rounds = stats.get("xins_round", (0,))[0]
+    print(f"every kind of group: {rounds} rounds")
+    assert 1 <= rounds <= 2 * math.log2(4500) + 4
+    assert "xfold" not in stats
+    _, stats = _every_group_run({"x_round_cap": 1})
+    assert "xfold" in stats
+    assert stats["xins_round"][0] >= 2
+
+
+def test_one_context_changing_shapes():
+    """One context through the every-group batch, a batch of three small
+    orphan-only documents (phase 1 only: fewer groups, smaller buffers), and
+    the first batch again: every result the oracle's, the first and the third
+    equal array for array."""
+    from tests import exact_model as M
+
+    big = _rank_docs(_every_group_docs())
+    docs = []
+    for k in range(3):
+        par, cls = M.random_doc(random.Random(60 + k), 300)
+        for r in (40 + k, 170, 299 - k):
+            par[r] = M.END
+        docs.append((par, cls))
+    small = _rank_docs(docs)
+    with abi.Weaver(0, options={"giant_min": 4096}) as w:
+        first = check_batch(w, *big, method=oracle.METHOD_LITERAL)
+        w.reset_kernel_stats()
+        w.set_profiling(True)
+        res = check_batch(w, *small, method=oracle.METHOD_LITERAL)
+        w.set_profiling(False)
+        stats = w.kernel_stats()
+        assert (res.status & abi.STATUS_ORPHAN).all()
+        assert stats["xsyn_resolve"][0] == 1 and "xins_round" not in stats and "geff" not in stats
+        again = check_batch(w, *big, method=oracle.METHOD_LITERAL)
+    for name in ("weave_perm", "visible_bits", "visible_count", "max_ts", "status"):
+        assert np.array_equal(getattr(first, name), getattr(again, name)), name
+    assert first.yarn_perm is None and again.yarn_perm is None  # (ids = ranks: no site bits)
+
+
 def _with_reverse_chain(off, idk, ck, a, L):
     """Ranks [a, a + L) of the one document: rank r caused by rank r + 1 (the
     last keeps its cause) -- a reverse chain of L early nodes."""
