@@ -14,6 +14,8 @@ order equals the full reweave).  There is no CPU weave in this module.
     map.cljc:246-247      weft (maps)               -> map_weft / weft_maps (cw_weft_maps)
     shared.cljc:259-266   refresh-caches            -> refresh_caches
     list.cljc:20-34       weave (all arities)       -> list_weave / weave_lists
+    list.cljc:29-34       weave 2/3-arity, incremental (s/weave-node)
+                                                    -> list_weave_node / insert_lists (cw_insert_lists)
     list.cljc:36-43       conj- / cons-             -> list_conj / list_cons
     list.cljc:48-72       hide? / ->edn / ->list    -> causal_list_to_edn / _to_list
 """
@@ -24,7 +26,7 @@ import threading
 
 import numpy as np
 
-from . import abi, pack
+from . import abi, abi_insert, pack
 
 
 class Keyword:
@@ -198,6 +200,106 @@ class _Tokens:
         except TypeError:
             key = ("r", repr(v))
         return self.t.setdefault(key, len(self.t))
+
+
+def insert_lists(items):
+    """s/insert with the incremental weave (c.list/weave's 2/3-arity over
+    s/weave-node, list.cljc:29-34, shared.cljc:225-241) for many ``(ct, node,
+    more)`` in ONE GPU call (cw_insert_lists): each ct's current ``weave`` is
+    packed as it stands and its tx spliced in, no reweave.  Same validations and
+    ex-info causes as ``insert``; a node already in the tree with the same body
+    returns its ct unchanged.  The yarns of a new ct come from the call's
+    yarn_perm, its rendered flags from the call's visible_bits.  Ids that need
+    the K128 layout (over 63 bits) raise a CauseError with cause "key-range":
+    ``list_weave`` reweaves such a ct."""
+    txs = []
+    for ct, node, more in items:
+        tx = [node] + list(more or [])
+        if len({(n[0][0], n[0][1]) for n in tx}) > 1:
+            raise CauseError("All nodes must belong to the same tx.", {"txs"})
+        txs.append(tx)
+    docs = [[(i, b[0], b[1]) for i, b in ct["nodes"].items()] for ct, _, _ in items]
+    try:
+        pk = pack.pack_lists([d + tx for d, tx in zip(docs, txs)], min_site_bits=1)  # one site ranking
+    except pack.KeyRangeError as e:  # ids over 63 bits: cw_insert_lists has no K128 form
+        raise CauseError(f"insert_lists takes ids that pack into 63 bits ({e}); "
+                         "list_weave reweaves such a ct", {"key-range"}) from e
+    tok = _Tokens()
+    vals = np.array([tok(n[2]) for d in pk.docs for n in d.nodes], np.uint64)
+    sel, tsel, perm, vis, yarn = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [], [], []
+    for d, ((ct, _, _), nodes, tx, pd) in enumerate(zip(items, docs, txs, pk.docs)):
+        lo, n = int(pk.offsets[d]), len(nodes)
+        sel.append(np.arange(lo, lo + n))
+        tsel.append(np.arange(lo + n, lo + n + len(tx)))
+        at = {nd[0]: s for s, nd in enumerate(nodes)}
+        perm += [at[nd[0]] for nd in ct["weave"]]
+        vis += [bool(v) for v in ct["_visible"]]
+        ys = ct.get("yarns") or {}
+        if sum(len(y) for y in ys.values()) != n:  # a ct without its ::yarns cache: spin (shared.cljc:121-132)
+            ys = {}
+            for nd in sorted(nodes, key=lambda nd: (nd[0][0], pack.java_str_key(nd[0][1]), nd[0][2])):
+                ys.setdefault(nd[0][1], []).append(nd)
+        for site in sorted(ys, key=lambda s: pd.site_rank[s]):
+            yarn += [at[nd[0]] for nd in ys[site]]
+    sel, tsel = np.concatenate(sel), np.concatenate(tsel)
+    N = len(sel)
+    if len(perm) != N or len(vis) != N:
+        raise CauseError("a ct's weave does not hold its nodes", {"weave-domain"})
+    bits = np.zeros((N + 31) // 32 * 32, np.uint8)
+    bits[:N] = vis
+    bits = np.packbits(bits, bitorder="little").view(np.uint32)
+    off = np.zeros(len(items) + 1, np.uint64)
+    off[1:] = np.cumsum([len(d) for d in docs])
+    toff = np.zeros(len(items) + 1, np.uint64)
+    toff[1:] = np.cumsum([len(t) for t in txs])
+    res = abi_insert.insert_lists(
+        weaver(), (off, pk.id_key[sel], pk.cause_key[sel], pk.kind[sel]), np.array(perm, np.uint32),
+        bits, (toff, pk.id_key[tsel], pk.cause_key[tsel], pk.kind[tsel], vals[tsel]), pk.layout,
+        yarn_perm=np.array(yarn, np.uint32), doc_value=vals[sel], columns=False)
+    rendered = res.weave.visible()
+    out = []
+    for d, ((ct, _, _), nodes, tx) in enumerate(zip(items, docs, txs)):
+        st = int(res.weave.status[d])
+        if st & abi.STATUS_DUP:
+            raise CauseError("This node is already in the tree and can't be changed.",
+                             {"append-only", "edits-not-allowed"})
+        if st & abi.STATUS_ORPHAN:
+            raise CauseError("The cause of this node is not in the tree.", {"cause-must-exist"})
+        if int(res.insert_pos[d]) == 0xFFFFFFFF:  # nothing inserted: the same node again
+            out.append(ct)
+            continue
+        lo, hi = int(res.offsets[d]), int(res.offsets[d + 1])
+        both = nodes + tx
+        new = dict(ct)
+        nm = dict(ct["nodes"])
+        for n in tx:
+            nm[n[0]] = (n[1], n[2])
+        new["nodes"] = nm
+        new["weave"] = [both[s] for s in res.weave.weave_perm[lo:hi]]
+        new["_visible"] = [bool(v) for v in rendered[lo:hi]]
+        yarns = {}
+        for s in res.weave.yarn_perm[lo:hi]:
+            yarns.setdefault(both[s][0][1], []).append(both[s])
+        new["yarns"] = yarns
+        new["_max_ts"] = int(res.weave.max_ts[d])
+        if tx[0][0][0] > ct["lamport_ts"]:  # shared.cljc:179-181
+            new["lamport_ts"] = tx[0][0][0]
+        out.append(new)
+    return out
+
+
+def list_weave_node(ct, node=None, more=None):
+    """A weave-fn for ``insert`` / ``append`` that weaves incrementally
+    (list.cljc:29-34): ``ct`` holds the tx in ::nodes already, its ``weave``
+    does not.  Without a node it is the full reweave (``list_weave``)."""
+    if node is None:
+        return list_weave(ct)
+    if node[0] not in ct["nodes"]:
+        return ct
+    tx = [node] + list(more or [])
+    base = dict(ct)
+    base["nodes"] = {i: b for i, b in ct["nodes"].items() if all(i != n[0] for n in tx)}
+    return insert_lists([(base, node, more)])[0]
 
 
 def merge_lists(pairs):

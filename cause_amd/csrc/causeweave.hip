@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "causeweave.h"
+#include "causeweave_insert.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
@@ -4525,6 +4526,10 @@ struct cw_ctx {
     DevLayout lists, maps;         // their layouts (lists.aux: the tiles' first documents)
     LookBack lb;                   // k_render's look-back words, for both calls
   } render;
+  struct Insert {                  // cw_insert_lists (listinsert.hip)
+    DevLayout docs, txs;           // doc_offsets, tx_offsets
+    LookBack lb;                   // k_insert_plan's look-back words
+  } insert;
 };
 
 namespace {
@@ -6281,6 +6286,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "listmerge.hip"
 #include "listweft.hip"
 #include "render.hip"
+#include "listinsert.hip"
 #include "dist.hip"
 
 namespace {
@@ -7826,6 +7832,12 @@ int cw_render_maps(cw_ctx *c, const cw_map_render_batch *b, cw_map_render_result
   if (!c) return -1;
   c->err.clear();
   return render_maps_impl(c, b, r, memspace);
+}
+
+int cw_insert_lists(cw_ctx *c, const cw_insert_batch *b, cw_insert_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return insert_lists_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,

@@ -13,6 +13,8 @@
  *
  * The JVM shim calls it from c.list/weave's 1-arity and from
  * s/refresh-caches; insert/append/merge reach it through a full reweave.
+ * The incremental insert (c.list/weave 2/3-arity, s/weave-node) is cw_insert_lists,
+ * in a header of its own: causeweave_insert.h.
  *
  * Conventions
  *  - Plain pointers and sizes, no torch/HIP types.  Every buffer is owned by the
