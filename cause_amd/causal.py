@@ -16,6 +16,8 @@ order equals the full reweave).  There is no CPU weave in this module.
     list.cljc:20-34       weave (all arities)       -> list_weave / weave_lists
     list.cljc:29-34       weave 2/3-arity, incremental (s/weave-node)
                                                     -> list_weave_node / insert_lists (cw_insert_lists)
+    map.cljc:29-45        weave 2/3-arity, incremental (s/weave-node on one key weave)
+                                                    -> map_weave_node / insert_maps (cw_insert_maps)
     list.cljc:36-43       conj- / cons-             -> list_conj / list_cons
     list.cljc:48-72       hide? / ->edn / ->list    -> causal_list_to_edn / _to_list
 """
@@ -26,7 +28,7 @@ import threading
 
 import numpy as np
 
-from . import abi, abi_insert, pack
+from . import abi, abi_insert, abi_map_insert, pack
 
 
 class Keyword:
@@ -714,6 +716,104 @@ def map_weave(ct, node=None, more=None):
     return weave_maps([ct])[0]
 
 
+def insert_maps(items):
+    """s/insert with the incremental map weave (c.map/weave's 2/3-arity over
+    s/weave-node, map.cljc:29-45) for many ``(ct, node, more)`` in ONE GPU call
+    (cw_insert_maps): each ct's key weaves are packed as they stand and its tx
+    woven in node by node, no reweave.  Same validations and ex-info causes as
+    ``insert``; a node already in the collection with the same body returns its
+    ct unchanged.  Only the key weaves the tx went to are rebuilt."""
+    txs = []
+    for ct, node, more in items:
+        tx = [node] + list(more or [])
+        if len({(n[0][0], n[0][1]) for n in tx}) > 1:
+            raise CauseError("All nodes must belong to the same tx.", {"txs"})
+        txs.append(tx)
+    docs = [[(i, b[0], b[1]) for i, b in ct["nodes"].items()] for ct, _, _ in items]
+    pm = pack.pack_maps([d + tx for d, tx in zip(docs, txs)])  # one site ranking, one key-token table
+    tok = _Tokens()
+    vals = np.array([tok(n[2]) for d in pm.docs for n in d], np.uint64)
+    ktok = {k: t for t, k in enumerate(pm.keys)}
+    sel, tsel = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)]
+    so, sc, sk, sa, sp = [0], [], [], [], []
+    for d, ((ct, _, _), nodes, tx) in enumerate(zip(items, docs, txs)):
+        lo, n = int(pm.offsets[d]), len(nodes)
+        sel.append(np.arange(lo, lo + n))
+        tsel.append(np.arange(lo + n, lo + n + len(tx)))
+        at = {nd[0]: s for s, nd in enumerate(nodes)}
+        words = {}
+        for k in ct["weave"]:
+            if k is None:
+                words[pack.NIL] = k
+            elif pack.valid_id(k):
+                words[1 << 63 | (0 if k == ROOT_ID else pm.layout.pack(k[0], pm.ranks[d][k[1]], k[2]))] = k
+            else:
+                words[ktok[k]] = k
+        for word in sorted(words):
+            k = words[word]
+            a = ct["_active"].get(k, BLANK)
+            sc.append(d)
+            sk.append(word)
+            sa.append(-1 if a is BLANK else at[a[0]])
+            sp += [0xFFFFFFFF] + [at[nd[0]] for nd in ct["weave"][k][1:]]
+            so.append(len(sp))
+    sel, tsel = np.concatenate(sel), np.concatenate(tsel)
+    off = np.zeros(len(items) + 1, np.uint64)
+    off[1:] = np.cumsum([len(d) for d in docs])
+    toff = np.zeros(len(items) + 1, np.uint64)
+    toff[1:] = np.cumsum([len(t) for t in txs])
+    if len(sp) != len(sel) + len(sk):
+        raise CauseError("a ct's weave does not hold its nodes", {"weave-domain"})
+    res = abi_map_insert.insert_maps(
+        weaver(), (off, pm.id_key[sel], pm.cause[sel], pm.cause_is_id[sel], pm.kind[sel]),
+        (np.array(so, np.uint64), np.array(sc, np.uint32), np.array(sk, np.uint64), np.array(sa, np.int64),
+         np.array(sp, np.uint32)),
+        (toff, pm.id_key[tsel], pm.cause[tsel], pm.cause_is_id[tsel], pm.kind[tsel], vals[tsel]),
+        coll_value=vals[sel], columns=False)
+    out = []
+    for d, ((ct, _, _), nodes, tx) in enumerate(zip(items, docs, txs)):
+        st = int(res.maps.status[d])
+        if st & abi.STATUS_DUP:
+            raise CauseError("This node is already in the tree and can't be changed.",
+                             {"append-only", "edits-not-allowed"})
+        if st & abi.STATUS_ORPHAN:
+            raise CauseError("The cause of this node is not in the tree.", {"cause-must-exist"})
+        if st & abi.STATUS_MAP_KEY:
+            raise CauseError(f"map outside the weave's domain (status {st})", {"weave-domain"})
+        t0 = int(toff[d])
+        if int(res.tx_seg[t0]) == 0xFFFFFFFF:  # nothing inserted: the same node again
+            out.append(ct)
+            continue
+        both = nodes + tx
+        new = dict(ct)
+        nm = dict(ct["nodes"])
+        for n in tx:
+            nm[n[0]] = (n[1], n[2])
+        new["nodes"] = nm
+        touched = sorted({int(s) for s in res.tx_seg[t0:t0 + len(tx)]})
+        w, a = _key_weaves(res.maps, touched, both, pm, d)
+        new["weave"] = {**ct["weave"], **w}
+        new["_active"] = {**ct["_active"], **a}
+        if tx[0][0][0] > ct["lamport_ts"]:  # shared.cljc:179-181
+            new["lamport_ts"] = tx[0][0][0]
+        out.append(new)
+    return out
+
+
+def map_weave_node(ct, node=None, more=None):
+    """A weave-fn for ``insert`` / ``append`` that weaves incrementally
+    (map.cljc:29-45): ``ct`` holds the tx in ::nodes already, its ``weave``
+    does not.  Without a node it is the full reweave (``map_weave``)."""
+    if node is None:
+        return map_weave(ct)
+    if node[0] not in ct["nodes"]:
+        return ct
+    tx = [node] + list(more or [])
+    base = dict(ct)
+    base["nodes"] = {i: b for i, b in ct["nodes"].items() if all(i != n[0] for n in tx)}
+    return insert_maps([(base, node, more)])[0]
+
+
 def active_node(ct, k):
     """map.cljc:47-59 (computed on the GPU with the weave)."""
     return ct["_active"].get(k, BLANK)
@@ -730,18 +830,19 @@ def map_count(ct):
     return sum(1 for n in ct["_active"].values() if n is not BLANK)
 
 
-def map_assoc(ct, k, v):
-    """map.cljc:75-81"""
+def map_assoc(ct, k, v, weave_fn=None):
+    """map.cljc:75-81.  weave_fn: the weave-fn ``append`` uses (default: the full
+    reweave, ``map_weave``; ``map_weave_node`` weaves the one node in)."""
     if v != map_get(ct, k):
-        return append(map_weave, ct, k, v)
+        return append(weave_fn or map_weave, ct, k, v)
     return ct
 
 
-def map_dissoc(ct, k):
-    """map.cljc:83-89"""
+def map_dissoc(ct, k, weave_fn=None):
+    """map.cljc:83-89.  weave_fn: as in ``map_assoc``."""
     v = map_get(ct, k)
     if v is not None and v is not False:
-        return append(map_weave, ct, k, HIDE)
+        return append(weave_fn or map_weave, ct, k, HIDE)
     return ct
 
 

@@ -43,6 +43,7 @@
 
 #include "causeweave.h"
 #include "causeweave_insert.h"
+#include "causeweave_map_insert.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
@@ -4530,6 +4531,11 @@ struct cw_ctx {
     DevLayout docs, txs;           // doc_offsets, tx_offsets
     LookBack lb;                   // k_insert_plan's look-back words
   } insert;
+  uint32_t map_insert_wave = 1;    // map_insert_wave: a wave per collection in cw_insert_maps (0: a workgroup)
+  struct MapInsert {               // cw_insert_maps (mapinsert.hip)
+    DevLayout colls, txs;          // coll_offsets, tx_offsets
+    LookBack lb;                   // k_map_insert's look-back words
+  } minsert;
 };
 
 namespace {
@@ -6283,6 +6289,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "mappack.hip"
 #include "mapmerge.hip"
 #include "mapweft.hip"
+#include "mapinsert.hip"
 #include "listmerge.hip"
 #include "listweft.hip"
 #include "render.hip"
@@ -7701,6 +7708,7 @@ static const struct {
     {"map_fused", &cw_ctx::map_fused, 0, UINT32_MAX},
     {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
     {"map_weft_fused", &cw_ctx::map_weft_fused, 0, 1},
+    {"map_insert_wave", &cw_ctx::map_insert_wave, 0, 1},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"list_weft_fused", &cw_ctx::list_weft_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
@@ -7838,6 +7846,12 @@ int cw_insert_lists(cw_ctx *c, const cw_insert_batch *b, cw_insert_result *r, in
   if (!c) return -1;
   c->err.clear();
   return insert_lists_impl(c, b, r, memspace);
+}
+
+int cw_insert_maps(cw_ctx *c, const cw_map_insert_batch *b, cw_map_insert_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return insert_maps_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,
