@@ -11,7 +11,12 @@ C ABI in batches:
     cw_weave_maps call (all maps), then the refs are resolved on the host;
   * ``history`` (the ``::history`` sorted log, :107-115): the reverse paths
     ``[id uuid]`` of every insertion sorted by id with cw_sort_keys (the
-    reference keeps the vector sorted by one binary-search insertion each).
+    reference keeps the vector sorted by one binary-search insertion each);
+  * ``invert_`` (:322-343), what ``undo_``, ``redo_`` and ``reset_`` end in:
+    every collection of the base (of many bases: ``invert_bases``) is packed
+    into ONE cw_invert call, which returns the inverting transaction; its nodes
+    are inserted like any other tx.  ``subhis``, ``get_next_tx_id`` and the undo
+    markers (:272-311, :354-409) are host logic.
 
 The transaction bookkeeping (``transact_``, ``flatten_value``, ``map_to_nodes``,
 ``list_to_nodes``, :117-268) is host logic that only builds nodes; it follows
@@ -21,11 +26,12 @@ reweave), with the insert-time checks of s/insert kept.
 """
 from __future__ import annotations
 
+import bisect
 import random
 
 import numpy as np
 
-from . import abi, causal as C, pack
+from . import abi, abi_invert, causal as C, pack
 
 REF_NS = "causal.collection.ref"      # base/core.cljc:57
 
@@ -46,7 +52,8 @@ def _no_weave(ct, node=None, more=None):
 def new_cb(rng=random):
     """base/core.cljc:39-53"""
     return {"lamport_ts": 1, "uuid": C._uid(rng, 21), "site_id": C.new_site_id(rng),
-            "history": [], "root_uuid": None, "collections": {}, "_rng": rng}
+            "history": [], "root_uuid": None, "collections": {}, "_rng": rng,
+            "first_undo_lamport_ts": None, "last_undo_lamport_ts": None, "last_redo_lamport_ts": None}
 
 
 def uuid_to_ref(uuid):
@@ -200,8 +207,227 @@ def transact_(cb, tx):
         if uuid is None:                                                # :207-212
             cb, uuid = add_collection_for(cb, value, is_root=True)
         cb, tx_index = _handle_value(cb, uuid, cause, value, tx_index)
+    return _end_tx(cb)
+
+
+def _end_tx(cb):
+    """:249-252 -- the lamport-ts bumped, the undo markers cleared."""
     cb = dict(cb)
     cb["lamport_ts"] = cb["lamport_ts"] + 1
+    cb["first_undo_lamport_ts"] = cb["last_undo_lamport_ts"] = cb["last_redo_lamport_ts"] = None
+    return cb
+
+
+# ------------------------------------------------------------- history ----
+def _id_key(i):
+    return (i[0], pack.java_str_key(i[1]), i[2])       # util.cljc:4-10
+
+
+def _sorted_history(cb):
+    """::history is kept sorted by id (:107-115); local transactions append in
+    that order already, merged ones may not."""
+    return sorted(cb["history"], key=lambda rp: _id_key(rp[0]))
+
+
+def tx_id_indexes(cb, tx_id):
+    """:272-289 -> (tx_start_i, tx_end_i) of the reverse paths of one tx-id in
+    the sorted history, (None, None) when it has none."""
+    if tx_id is None:
+        return None, None
+    hist = _sorted_history(cb)
+    keys = [_id_key(rp[0]) for rp in hist]
+    start = bisect.bisect_left(keys, _id_key(tuple(tx_id) + (0,)))
+    if start == len(hist) or hist[start][0] != tuple(tx_id) + (0,):
+        return None, None
+    end = start
+    while end + 1 < len(hist) and hist[end + 1][0][:2] == tuple(tx_id):
+        end += 1
+    return start, end
+
+
+_SAME = object()
+
+
+def subhis(cb, start_tx_id, end_tx_id=_SAME):
+    """:291-311 -- the history between two tx-ids, inclusive; None is the start
+    or the end; one argument slices out one tx-id."""
+    if end_tx_id is _SAME:
+        end_tx_id = start_tx_id
+    hist = _sorted_history(cb)
+    start_i, end_i = tx_id_indexes(cb, start_tx_id)
+    if start_tx_id != end_tx_id:
+        _, end_i = tx_id_indexes(cb, end_tx_id)
+    if (start_tx_id is not None and start_i is None) or (end_tx_id is not None and end_i is None):
+        return []
+    return hist[start_i or 0:end_i + 1] if end_i is not None else hist[start_i or 0:]
+
+
+def get_next_tx_id(cb, last_undo_or_redo_ts):
+    """:354-369 -- the tx-id next in line to be undone or redone."""
+    remaining = subhis(cb, None, (last_undo_or_redo_ts - 1, cb["site_id"])) if last_undo_or_redo_ts \
+        else _sorted_history(cb)
+    for (ts, site, _), _ in reversed(remaining):
+        if site == cb["site_id"]:
+            return (ts, site)
+    return None
+
+
+def invert_path(path):
+    """:313-320 -- path = {"uuid": ..., "node": (id, cause, value)} -> tx-part."""
+    uuid, (nid, cause, value) = path["uuid"], path["node"]
+    if value == C.HIDE or value == C.H_HIDE:
+        return (uuid, cause, C.H_SHOW)
+    if value == C.H_SHOW:
+        return (uuid, cause, C.H_HIDE)
+    return (uuid, nid, C.H_HIDE)
+
+
+def _gpu_invert(*args):
+    return abi_invert.invert(C.weaver(), *args)
+
+
+def _selection(cb, history_slice):
+    """A slice as cw_invert takes it: (lo id, hi id, sites).  subhis filtered by
+    site is every reverse path of an id range with those sites; any other
+    subset of the history is refused."""
+    ids = [i for i, _ in history_slice]
+    lo, hi = min(ids, key=_id_key), max(ids, key=_id_key)
+    sites = {i[1] for i in ids}
+    inside = sum(1 for i, _ in cb["history"]
+                 if _id_key(lo) <= _id_key(i) <= _id_key(hi) and i[1] in sites)
+    if inside != len(set(ids)):
+        raise ValueError("history_slice is not a site-filtered range of the history")
+    return lo, hi, sites
+
+
+def _pack_bases(cbs, sels):
+    """Every collection of every base as one cw_invert batch: lists and maps
+    together, one key layout and one site ranking, ref_doc from the ref values."""
+    ids = [C.ROOT_ID]
+    for cb in cbs:
+        ids.append((cb["lamport_ts"], cb["site_id"], 0))
+        for ct in cb["collections"].values():
+            for nid, (cause, _) in ct["nodes"].items():
+                ids.append(nid)
+                if pack.valid_id(cause):
+                    ids.append(cause)
+    sites = sorted({i[1] for i in ids}, key=pack.java_str_key)
+    rank = {s: r for r, s in enumerate(sites)}
+    most = max([len(cb["history"]) for cb in cbs] + [i[2] + 1 for i in ids])
+    lay = pack.KeyLayout(max(1, max(i[0] for i in ids).bit_length()), max(1, (len(sites) - 1).bit_length()),
+                         max(1, (most - 1).bit_length()))
+    if lay.key_bits > 63:
+        raise pack.KeyRangeError(f"ids need {lay.key_bits} bits (> 63)")
+    pk = lambda i: 0 if i == C.ROOT_ID else lay.pack(i[0], rank[i[1]], i[2])
+    tok = {}
+    off, boff, docs = [0], [0], []
+    idk, ca, ci, kd, rf = [], [], [], [], []
+    for cb in cbs:
+        uuids = list(cb["collections"])
+        index = {u: len(docs) + k for k, u in enumerate(uuids)}
+        for u in uuids:
+            ct = cb["collections"][u]
+            nodes = [(nid, cause, value) for nid, (cause, value) in ct["nodes"].items()]
+            docs.append((u, nodes))
+            for nid, cause, value in nodes:
+                idk.append(pk(nid))
+                k = pack.kind_of(value)
+                if ct["type"] == "list":
+                    if nid == C.ROOT_ID and cause is None and value is None:
+                        k |= pack.KIND_ROOT
+                    ca.append(pack.NIL if cause is None else pk(cause) if pack.is_id(cause) else pack.NON_ID_CAUSE)
+                    ci.append(1)
+                elif pack.valid_id(cause):
+                    ca.append(pk(cause))
+                    ci.append(1)
+                elif cause is None:
+                    ca.append(0)
+                    ci.append(2)
+                else:
+                    ca.append(tok.setdefault(cause, len(tok)))
+                    ci.append(0)
+                kd.append(k)
+                rf.append(index.get(ref_to_uuid(value), abi_invert.U32_MAX) if is_ref(value) else abi_invert.U32_MAX)
+            off.append(len(idk))
+        boff.append(len(docs))
+    W, G = abi_invert.mask_words(lay.site_bits), len(cbs)
+    lo_a, hi_a = np.ones(G, np.uint64), np.zeros(G, np.uint64)
+    masks, ntx = np.zeros(G * W, np.uint64), np.zeros(G, np.uint64)
+    for g, (cb, sel) in enumerate(zip(cbs, sels)):
+        ntx[g] = lay.pack(cb["lamport_ts"], rank[cb["site_id"]], 0)
+        if sel is None:          # an empty slice: lo > hi selects nothing
+            continue
+        lo_a[g], hi_a[g] = pk(sel[0]), pk(sel[1])
+        for s in sel[2]:
+            masks[g * W + rank[s] // 64] |= np.uint64(1 << (rank[s] % 64))
+    args = (np.array(off, np.uint64), np.array(idk, np.uint64), np.array(ca, np.uint64), np.array(kd, np.uint8),
+            np.array(ci, np.uint8), np.array(rf, np.uint32), lay, np.array(boff, np.uint64), lo_a, hi_a, masks,
+            ntx)
+    return args, docs
+
+
+def invert_bases(cbs, slices, invert_fn=None):
+    """invert- (:322-343) for many bases in ONE cw_invert call: every node of
+    each slice becomes an inverting tx-part, one part per [uuid cause], nested
+    collections that are about to be hidden dropped, the rest transacted at the
+    base's lamport-ts.  invert_fn: the call (default: the GPU), taking
+    abi_invert.invert's arguments after the Weaver."""
+    sels = [_selection(cb, sl) if sl else None for cb, sl in zip(cbs, slices)]
+    args, docs = _pack_bases(cbs, sels)
+    res = (invert_fn or _gpu_invert)(*args)
+    if np.any(res.status):
+        raise C.CauseError("the inverting tx does not fit the key layout", {"key-range"})
+    boff, po, ntx = args[7], res.part_offsets, args[11]
+    out = []
+    for g, cb in enumerate(cbs):
+        parts = []
+        for d in range(int(boff[g]), int(boff[g + 1])):
+            uuid, nodes = docs[d]
+            for j in range(int(po[d]), int(po[d + 1])):
+                nid, cause, value = nodes[int(res.inv_src[j])]
+                special = pack.kind_of(value) != pack.KIND_NORMAL
+                kw = C.H_HIDE if int(res.inv_kind[j]) == pack.KIND_HHIDE else C.H_SHOW
+                parts.append((int(res.inv_id[j]) - int(ntx[g]), uuid, cause if special else nid, kw))
+        for tx_index, uuid, cause, kw in sorted(parts, key=lambda p: p[0]):   # transact- (:232-252)
+            cb = _insert(cb, uuid, [new_node(cb, tx_index, cause, kw)[1]])
+        out.append(_end_tx(cb))
+    return out
+
+
+def invert_(cb, history_slice, invert_fn=None):
+    """:322-343"""
+    return invert_bases([cb], [history_slice], invert_fn)[0]
+
+
+def reset_(cb, tx_id, site_ids, invert_fn=None):
+    """:345-352 -- every transaction of ``site_ids`` back to ``tx_id`` undone."""
+    sites = set(site_ids)
+    return invert_(cb, [rp for rp in subhis(cb, tx_id, None) if rp[0][1] in sites], invert_fn)
+
+
+def _local(cb, tx_id):
+    return [rp for rp in subhis(cb, tx_id) if rp[0][1] == cb["site_id"]]
+
+
+def undo_(cb, invert_fn=None):
+    """:375-390 -- the next transaction of the undo stack undone."""
+    next_id = get_next_tx_id(cb, cb.get("last_undo_lamport_ts"))
+    if next_id is None:
+        return cb
+    first = cb.get("first_undo_lamport_ts") or next_id[0]
+    cb = invert_(cb, _local(cb, next_id), invert_fn)
+    cb.update(first_undo_lamport_ts=first, last_undo_lamport_ts=next_id[0], last_redo_lamport_ts=None)
+    return cb
+
+
+def redo_(cb, invert_fn=None):
+    """:392-409 -- the last undone transaction done again, never past the first undo."""
+    next_id = get_next_tx_id(cb, cb.get("last_redo_lamport_ts"))
+    first, last = cb.get("first_undo_lamport_ts"), cb.get("last_undo_lamport_ts")
+    if first is None or next_id is None or next_id[0] <= first:
+        return cb
+    cb = invert_(cb, _local(cb, next_id), invert_fn)
+    cb.update(first_undo_lamport_ts=first, last_undo_lamport_ts=last, last_redo_lamport_ts=next_id[0])
     return cb
 
 

@@ -44,6 +44,7 @@
 #include "causeweave.h"
 #include "causeweave_insert.h"
 #include "causeweave_map_insert.h"
+#include "causeweave_invert.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
@@ -4536,6 +4537,11 @@ struct cw_ctx {
     DevLayout colls, txs;          // coll_offsets, tx_offsets
     LookBack lb;                   // k_map_insert's look-back words
   } minsert;
+  uint32_t invert_cap = 4096;      // invert_cap: most candidates of a base that cw_invert finishes in LDS
+  struct Invert {                  // cw_invert (invert.hip)
+    DevLayout docs, bases;         // doc_offsets, base_offsets
+    LookBack lb_tiles, lb_docs;    // k_invert_compact's and k_invert_write's look-back words
+  } invert;
 };
 
 namespace {
@@ -6294,6 +6300,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "listweft.hip"
 #include "render.hip"
 #include "listinsert.hip"
+#include "invert.hip"
 #include "dist.hip"
 
 namespace {
@@ -7709,6 +7716,7 @@ static const struct {
     {"map_merge_fused", &cw_ctx::map_merge_fused, 0, 1},
     {"map_weft_fused", &cw_ctx::map_weft_fused, 0, 1},
     {"map_insert_wave", &cw_ctx::map_insert_wave, 0, 1},
+    {"invert_cap", &cw_ctx::invert_cap, 1, 4096},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"list_weft_fused", &cw_ctx::list_weft_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
@@ -7852,6 +7860,12 @@ int cw_insert_maps(cw_ctx *c, const cw_map_insert_batch *b, cw_map_insert_result
   if (!c) return -1;
   c->err.clear();
   return insert_maps_impl(c, b, r, memspace);
+}
+
+int cw_invert(cw_ctx *c, const cw_invert_batch *b, cw_invert_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return invert_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,
