@@ -16,7 +16,13 @@ C ABI in batches:
     every collection of the base (of many bases: ``invert_bases``) is packed
     into ONE cw_invert call, which returns the inverting transaction; its nodes
     are inserted like any other tx.  ``subhis``, ``get_next_tx_id`` and the undo
-    markers (:272-311, :354-409) are host logic.
+    markers (:272-311, :354-409) are host logic;
+  * ``bases_to_edn``: ``cb_to_edn`` for many bases at once, the refs resolved on
+    the device too: every list of every base in ONE cw_weave_lists and ONE
+    cw_render_lists call, every map in ONE cw_weave_maps and ONE cw_render_maps
+    call, both rendered with the ref column as the value, and ONE
+    cw_render_bases call that turns the entry table into a depth-first token
+    stream per base.  The host rebuilds the nested values with one stack pass.
 
 The transaction bookkeeping (``transact_``, ``flatten_value``, ``map_to_nodes``,
 ``list_to_nodes``, :117-268) is host logic that only builds nodes; it follows
@@ -31,7 +37,7 @@ import random
 
 import numpy as np
 
-from . import abi, abi_invert, causal as C, pack
+from . import abi, abi_invert, abi_render_bases as RB, causal as C, pack
 
 REF_NS = "causal.collection.ref"      # base/core.cljc:57
 
@@ -486,6 +492,114 @@ def cb_to_edn(cb):
     if root is None:
         return None, cb
     return _ct_edn(cb, root, {root["uuid"]}), cb
+
+
+# ---------------------------------------------------- cb->edn of many bases ----
+def _gpu_render_bases(*args):
+    return RB.render_bases(C.weaver(), *args)
+
+
+def _collect_docs(cbs):
+    """The documents of a batch of bases, lists first, then maps: [(base, uuid,
+    nodes)], the number of lists, and each base's root document (D: none)."""
+    picked = {"list": [], "map": []}
+    for g, cb in enumerate(cbs):
+        for u, ct in cb["collections"].items():
+            picked[ct["type"]].append((g, u, [(i, b[0], b[1]) for i, b in ct["nodes"].items()]))
+    docs = picked["list"] + picked["map"]
+    index = {(g, u): d for d, (g, u, _) in enumerate(docs)}
+    roots = np.array([index.get((g, cb["root_uuid"]), len(docs)) for g, cb in enumerate(cbs)], np.uint32)
+    return docs, len(picked["list"]), index, roots
+
+
+def _ref_column(docs, index):
+    """ref_doc per node, in document order: U32_MAX for a plain value, the
+    batch-wide document of a ref's collection, n_docs for a ref to a collection
+    the base does not hold (the reference's get-in gives nil)."""
+    D = len(docs)
+    return np.array([index.get((g, ref_to_uuid(n[2])), D) if is_ref(n[2]) else RB.U32_MAX
+                     for g, _, nodes in docs for n in nodes], np.uint32)
+
+
+def _gpu_entries(docs, n_lists, refs):
+    """The entry table of the documents, woven and rendered on the GPU with the
+    ref column as the value: (ent_offsets, ent_ref, ent_src, ent_key), ent_key a
+    list with the map key of every map entry (None for a list entry)."""
+    w = C.weaver()
+    lists, maps = [nodes for _, _, nodes in docs[:n_lists]], [nodes for _, _, nodes in docs[n_lists:]]
+    n_list_nodes = sum(len(x) for x in lists)
+    off, ref, src, key = [np.zeros(1, np.uint64)], [], [], []
+    if lists:
+        try:
+            b = pack.pack_lists(lists)
+            res = w.weave_lists(b.offsets, b.id_key, b.cause_key, b.kind, b.layout, yarns=False)
+        except pack.KeyRangeError:  # ids over 63 bits: the K128 layout
+            b = pack.pack_lists_k128(lists)
+            res = w.weave_lists_k128(b.offsets, b.id_key, b.cause_key, b.kind, yarns=False)
+        if np.any(res.status & (abi.STATUS_DUP | abi.STATUS_INTERNAL)):
+            raise C.CauseError("document outside the weave's domain", {"weave-domain"})
+        r = w.render_lists(b.offsets, res.weave_perm, res.visible_bits, refs[:n_list_nodes])
+        off.append(r.offsets[1:])
+        ref.append(r.value), src.append(r.src)
+        key += [None] * len(r.src)
+    if maps:
+        pm = pack.pack_maps(maps)
+        res = w.weave_maps(pm.offsets, pm.id_key, pm.cause, pm.cause_is_id, pm.kind, pm.token_bits,
+                           pm.layout.key_bits)
+        if np.any(res.status & (abi.STATUS_DUP | abi.STATUS_MAP_KEY | abi.STATUS_INTERNAL)):
+            raise C.CauseError("map outside the weave's domain", {"weave-domain"})
+        r = w.render_maps(len(maps), res.seg_coll, res.seg_key, res.seg_active, pm.offsets, refs[n_list_nodes:])
+        off.append(r.offsets[1:] + off[-1][-1])
+        ref.append(r.value), src.append(r.src)
+        for d in range(len(maps)):
+            key += [C._seg_key(k, pm, d) for k in r.key[int(r.offsets[d]):int(r.offsets[d + 1])].tolist()]
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)
+    return cat(off, np.uint64), cat(ref, np.uint32), cat(src, np.uint32), key
+
+
+def bases_to_edn(cbs, render_fn=None, entries_fn=None):
+    """cb->edn (base/core.cljc:92-96) of many bases -> [edn].  Every collection
+    of every base goes through one weave and one render call per kind, the refs
+    are resolved by ONE cw_render_bases call, and each base's nested value is
+    rebuilt from its token stream with one stack pass.  A base the call flags
+    (a collection referred to twice, a reference cycle) goes through cb_to_edn.
+    render_fn: the call (default: the GPU), taking abi_render_bases.render_bases'
+    arguments after the Weaver.  entries_fn: what makes the entry table
+    (default: the GPU weaves and renders), taking _gpu_entries' arguments."""
+    cbs = list(cbs)
+    docs, n_lists, index, roots = _collect_docs(cbs)
+    ent_off, ent_ref, ent_src, ent_key = (entries_fn or _gpu_entries)(docs, n_lists, _ref_column(docs, index))
+    res = (render_fn or _gpu_render_bases)(ent_off, ent_ref, roots)
+    kinds, tdoc, tent = res.tok_kind.tolist(), res.tok_doc.tolist(), res.tok_entry.tolist()
+    src, bo = ent_src.tolist(), res.base_tok_offsets.tolist()
+    map0 = int(ent_off[n_lists])          # the first entry of a map
+    out = []
+    for g, cb in enumerate(cbs):
+        if int(res.base_status[g]) & RB.STATUS_REF_SHARED:
+            out.append(cb_to_edn(cb)[0])
+            continue
+        value, stack = None, []           # stack: the open collections, innermost last
+
+        def put(e, v):                    # entry e of the innermost collection gets the value v
+            if e >= map0:
+                stack[-1][ent_key[e]] = v
+            else:
+                stack[-1].append(v)
+
+        for t in range(bo[g], bo[g + 1]):
+            k, d, e = kinds[t], tdoc[t], tent[t]
+            if k == RB.TOK_OPEN:
+                stack.append([] if d < n_lists else {})
+            elif k == RB.TOK_CLOSE:
+                value = stack.pop()
+                if stack:
+                    put(e, value)
+            elif k == RB.TOK_LEAF:
+                put(e, docs[d][2][src[e]][2])
+            else:
+                put(e, None)
+        out.append(value)
+    return out
 
 
 def history(cb):

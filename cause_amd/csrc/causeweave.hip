@@ -45,6 +45,7 @@
 #include "causeweave_insert.h"
 #include "causeweave_map_insert.h"
 #include "causeweave_invert.h"
+#include "causeweave_render_bases.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
@@ -4542,6 +4543,10 @@ struct cw_ctx {
     DevLayout docs, bases;         // doc_offsets, base_offsets
     LookBack lb_tiles, lb_docs;    // k_invert_compact's and k_invert_write's look-back words
   } invert;
+  struct RenderBases {             // cw_render_bases (renderbase.hip)
+    DevLayout docs;                // ent_offsets
+    LookBack lb_tiles, lb_bases;   // k_rb_compact's and k_rb_size's look-back words
+  } rbase;
 };
 
 namespace {
@@ -6301,6 +6306,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "render.hip"
 #include "listinsert.hip"
 #include "invert.hip"
+#include "renderbase.hip"
 #include "dist.hip"
 
 namespace {
@@ -7866,6 +7872,12 @@ int cw_invert(cw_ctx *c, const cw_invert_batch *b, cw_invert_result *r, int mems
   if (!c) return -1;
   c->err.clear();
   return invert_impl(c, b, r, memspace);
+}
+
+int cw_render_bases(cw_ctx *c, const cw_render_bases_batch *b, cw_render_bases_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return render_bases_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,
