@@ -22,12 +22,19 @@ C ABI in batches:
     cw_render_lists call, every map in ONE cw_weave_maps and ONE cw_render_maps
     call, both rendered with the ref column as the value, and ONE
     cw_render_bases call that turns the entry table into a depth-first token
-    stream per base.  The host rebuilds the nested values with one stack pass.
+    stream per base.  The host rebuilds the nested values with one stack pass;
+  * ``transact_bases``: ``transact-`` (:100-252) for many bases at once: the
+    values of every transaction flattened into token streams on the host
+    (``tokenize_tx``: one type test per tx-part, the three validation errors)
+    and ONE cw_transact call that assigns the tx-index, allocates a collection
+    per nested list or map, chains the lists and splices the strings.  The host
+    draws the uuids and applies the nodes run by run through ``_insert``.
 
-The transaction bookkeeping (``transact_``, ``flatten_value``, ``map_to_nodes``,
-``list_to_nodes``, :117-268) is host logic that only builds nodes; it follows
-the reference clause by clause and defers the weave: collections are woven
-when materialised (insertion in any causal order equals the full
+``transact_`` (with ``flatten_value``, ``map_to_nodes``, ``list_to_nodes``,
+:117-268) is the same bookkeeping for one base as a host recursion, one node at
+a time; it follows the reference clause by clause and is what ``transact_bases``
+is tested against.  Both defer the weave: collections are woven when
+materialised (insertion in any causal order equals the full
 reweave), with the insert-time checks of s/insert kept.
 """
 from __future__ import annotations
@@ -37,7 +44,7 @@ import random
 
 import numpy as np
 
-from . import abi, abi_invert, abi_render_bases as RB, causal as C, pack
+from . import abi, abi_invert, abi_render_bases as RB, abi_transact, causal as C, pack
 
 REF_NS = "causal.collection.ref"      # base/core.cljc:57
 
@@ -222,6 +229,169 @@ def _end_tx(cb):
     cb["lamport_ts"] = cb["lamport_ts"] + 1
     cb["first_undo_lamport_ts"] = cb["last_undo_lamport_ts"] = cb["last_redo_lamport_ts"] = None
     return cb
+
+
+# ------------------------------------------- transact- of many bases ----
+def _gpu_transact(*args):
+    return abi_transact.transact(C.weaver(), *args)
+
+
+def _is_string(v):
+    return isinstance(v, str) and not isinstance(v, Char)
+
+
+def tokenize_tx(cb, tx):
+    """The value walk of transact- (:185-252) as the token stream cw_transact
+    takes: one type test per tx-part (merge-value-into-parent-collection?,
+    :184-190), no tx-index, no collection, no chaining.  -> [(kind, uuid or
+    length, cause, value, parent)]: the uuid of a PART's collection, the length
+    of a STR; the cause as the tx gives it (a part's, or a map child's key), with
+    ``C.ROOT_ID`` where list-to-nodes starts from the root; parent: the token that
+    opens the enclosing group (a CLOSE's: its own opener), -1 for a part.  The
+    three validate-tx-part errors are raised as ``transact_`` raises them."""
+    T = abi_transact
+    toks = []
+
+    def child(v, key, parent):
+        if _is_string(v):
+            toks.append((T.TX_STR, len(v), key, v, parent))
+        elif _is_map(v) or _seqable(v):
+            me = len(toks)
+            toks.append((T.TX_OPEN_MAP if _is_map(v) else T.TX_OPEN_LIST, 0, key, None, parent))
+            contents(v, me)
+            toks.append((T.TX_CLOSE, 0, None, None, me))
+        else:
+            toks.append((T.TX_LEAF, 0, key, v, parent))
+
+    def contents(v, parent):
+        if _is_map(v):
+            for k, x in v.items():
+                child(x, k, parent)
+        else:
+            for x in _elements(v, False):
+                child(x, None, parent)
+
+    has_root = cb["root_uuid"] is not None
+    for uuid, cause, value in tx:
+        if uuid is not None and not has_root:                          # :219-221
+            raise C.CauseError("Please transact a root collection first by setting uuid "
+                               "and cause to nil", set())
+        if uuid is not None and uuid not in cb["collections"]:          # :222-224
+            raise C.CauseError("Collection with provided uuid not found", set())
+        if uuid is None and not (_is_map(value) or isinstance(value, (list, tuple))):
+            raise C.CauseError("Root node must satisfy the coll? predicate", set())
+        me = len(toks)
+        if uuid is None:                                                # :207-212
+            kind, to_map, has_root = (T.TX_ROOT_MAP if _is_map(value) else T.TX_ROOT_LIST), _is_map(value), True
+        else:
+            kind, to_map = T.TX_PART, cb["collections"][uuid]["type"] == "map"
+        merge = (cause is None and _is_map(value) and to_map) or \
+            (not _is_map(value) and _seqable(value) and not to_map)
+        if merge and not to_map and cause is None:
+            cause = C.ROOT_ID                                           # list-to-nodes (:142)
+        toks.append((kind, uuid, cause, None, -1))
+        if not merge:
+            child(value, cause, me)
+        elif _is_string(value):
+            toks.append((T.TX_STR, len(value), None, value, me))
+        else:
+            contents(value, me)
+        toks.append((T.TX_CLOSE, 0, None, None, me))
+    return toks
+
+
+def transact_bases(cbs, txs, transact_fn=None):
+    """``[transact_(cb, tx) for cb, tx in zip(cbs, txs)]`` with the nodes of every
+    base made by ONE cw_transact call: the token streams of ``tokenize_tx`` in,
+    the node columns out; the uuids of the new collections are drawn from each
+    base's rng in creation order, the nodes go through ``_insert`` run by run in
+    the order of the reference's inserts (a group is inserted when it closes),
+    and ``_end_tx`` ends the transaction.  transact_fn: the call (default: the
+    GPU), taking abi_transact.transact's arguments after the Weaver."""
+    T = abi_transact
+    cbs = list(cbs)
+    streams = [tokenize_tx(cb, tx) for cb, tx in zip(cbs, txs)]
+    # one key layout and one site ranking for every id the call sees or makes
+    ids = [C.ROOT_ID] + [(cb["lamport_ts"], cb["site_id"], 0) for cb in cbs]
+    ids += [t[2] for s in streams for t in s if pack.valid_id(t[2])]
+    sites = sorted({i[1] for i in ids}, key=pack.java_str_key)
+    rank = {s: r for r, s in enumerate(sites)}
+    most = max([sum(t[1] if t[0] == T.TX_STR else 1 for t in s) for s in streams] + [i[2] + 1 for i in ids])
+    lay = pack.KeyLayout(max(1, max(i[0] for i in ids).bit_length()), max(1, (len(sites) - 1).bit_length()),
+                         max(1, (most - 1).bit_length()))
+    if lay.key_bits > 63:
+        raise pack.KeyRangeError(f"ids need {lay.key_bits} bits (> 63)")
+    pk = lambda i: 0 if i == C.ROOT_ID else lay.pack(i[0], rank[i[1]], i[2])
+    keys = {}
+    doff, toff, ism, ntx = [0], [0], [], []
+    kind, arg, cause, cii, vkind = [], [], [], [], []
+    for cb, s in zip(cbs, streams):
+        index = {u: doff[-1] + k for k, u in enumerate(cb["collections"])}
+        ism += [ct["type"] == "map" for ct in cb["collections"].values()]
+        ntx.append(lay.pack(cb["lamport_ts"], rank[cb["site_id"]], 0))
+        for k, a, c, v, _ in s:
+            kind.append(k)
+            arg.append(index[a] if k == T.TX_PART else a if k == T.TX_STR else 0)
+            if pack.valid_id(c):
+                cause.append(pk(c)), cii.append(1)
+            elif c is None:      # the nil key of a map; nil as a list part's cause
+                cause.append(pack.NIL), cii.append(2)
+            elif pack.is_id(c):  # (an id that is not a valid one: no node has it)
+                cause.append(pack.NON_ID_CAUSE), cii.append(1)
+            else:
+                cause.append(keys.setdefault(c, len(keys))), cii.append(0)
+            vkind.append(pack.kind_of(v) if k == T.TX_LEAF else 0)
+        doff.append(len(ism))
+        toff.append(len(kind))
+    res = (transact_fn or _gpu_transact)(np.array(doff, np.uint64), np.array(ism, np.uint8), lay,
+                                         np.array(ntx, np.uint64), np.array(toff, np.uint64),
+                                         np.array(kind, np.uint8), np.array(arg, np.uint32),
+                                         np.array(cause, np.uint64), np.array(cii, np.uint8),
+                                         np.array(vkind, np.uint8))
+    if np.any(res.base_status & abi.STATUS_KEY_RANGE):
+        raise C.CauseError("the transaction does not fit the key layout", {"key-range"})
+    if np.any(res.base_status):
+        raise C.CauseError("tokenize_tx made a stream that cw_transact refuses", {"internal"})
+    D, no = len(ism), res.node_offsets.tolist()
+    nid, nca, src, sub, ref, run, nkd = (x.tolist() for x in (res.node_id, res.node_cause, res.node_src, res.node_sub,
+                                                               res.node_ref, res.node_run, res.node_kind))
+    out = []
+    for g, (cb, s) in enumerate(zip(cbs, streams)):
+        t0, c0, c1 = toff[g], int(res.base_new_offsets[g]), int(res.base_new_offsets[g + 1])
+        uuids = list(cb["collections"])
+        for c in range(c0, c1):      # add-collection-of-this-values-type-to-cb (:117-126), in creation order
+            k = s[int(res.new_open[c]) - t0][0]
+            cb, u = add_collection_for(cb, {} if k in (T.TX_OPEN_MAP, T.TX_ROOT_MAP) else [],
+                                       is_root=k in (T.TX_ROOT_MAP, T.TX_ROOT_LIST))
+            uuids.append(u)
+        doc_uuid = lambda d: uuids[d - doff[g]] if d < D else uuids[len(uuids) - (c1 - c0) + (d - D - c0)]
+        runs = []                    # (the token that closes the run's group, uuid, nodes)
+        for d in list(range(doff[g], doff[g + 1])) + list(range(D + c0, D + c1)):
+            for j in range(no[d], no[d + 1]):
+                if nkd[j] & pack.KIND_ROOT:
+                    continue         # new-causal-list made the root
+                tok = s[src[j] - t0]
+                made_by = tok[4] if tok[0] == T.TX_CLOSE else src[j] - t0   # a ref: the OPEN_* that its CLOSE closes
+                k, a, c, v, parent = s[made_by]
+                grp = s[parent]
+                if run[j]:
+                    runs.append((parent, doc_uuid(d), []))
+                in_map = grp[0] in (T.TX_OPEN_MAP, T.TX_ROOT_MAP) or \
+                    (grp[0] == T.TX_PART and cb["collections"][grp[1]]["type"] == "map")
+                if in_map:
+                    node_cause = c
+                elif run[j]:         # the group's initial cause
+                    node_cause = grp[2] if grp[0] in (T.TX_PART, T.TX_ROOT_LIST) else C.ROOT_ID
+                else:                # chained: a node of this transaction
+                    node_cause = (cb["lamport_ts"], cb["site_id"], nca[j] - int(ntx[g]))
+                value = uuid_to_ref(doc_uuid(ref[j])) if k in (T.TX_OPEN_LIST, T.TX_OPEN_MAP) else \
+                    v if k == T.TX_LEAF or in_map else Char(v[sub[j]])
+                runs[-1][2].append(((cb["lamport_ts"], cb["site_id"], nid[j] - int(ntx[g])), node_cause, value))
+        close_of = {t[4]: i for i, t in enumerate(s) if t[0] == T.TX_CLOSE}
+        for _, u, nodes in sorted(runs, key=lambda r: close_of[r[0]]):
+            cb = _insert(cb, u, nodes)
+        out.append(_end_tx(cb))
+    return out
 
 
 # ------------------------------------------------------------- history ----

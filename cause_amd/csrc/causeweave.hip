@@ -46,6 +46,7 @@
 #include "causeweave_map_insert.h"
 #include "causeweave_invert.h"
 #include "causeweave_render_bases.h"
+#include "causeweave_transact.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
@@ -4547,6 +4548,13 @@ struct cw_ctx {
     DevLayout docs;                // ent_offsets
     LookBack lb_tiles, lb_bases;   // k_rb_compact's and k_rb_size's look-back words
   } rbase;
+  struct Transact {                // cw_transact (transact.hip)
+    DevLayout toks, docs;          // tok_offsets, base_doc_offsets
+    LookBack lb_scan, lb_rank, lb_count, lb_bases, lb_runs, lb_docs;  // one set of look-back words a scanning kernel
+    void *pin = nullptr;           // pinned: the offsets of a call, read back at its one wait
+    size_t pin_bytes = 0;
+  } transact;
+  uint32_t transact_cap = 4096;    // transact_cap: most tokens of a base that cw_transact sorts in LDS
 };
 
 namespace {
@@ -6307,6 +6315,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "listinsert.hip"
 #include "invert.hip"
 #include "renderbase.hip"
+#include "transact.hip"
 #include "dist.hip"
 
 namespace {
@@ -7679,6 +7688,7 @@ void cw_ctx_destroy(cw_ctx *c) {
   for (auto &kv : c->bufs)
     if (kv.second.p) (void)hipFree(kv.second.p);
   if (c->pinned) (void)hipHostFree(c->pinned);
+  if (c->transact.pin) (void)hipHostFree(c->transact.pin);
   if (c->pin_small) (void)hipHostFree(c->pin_small);
   if (c->pin_status) (void)hipHostFree(c->pin_status);
   if (c->ev_status) (void)hipEventDestroy(c->ev_status);
@@ -7723,6 +7733,7 @@ static const struct {
     {"map_weft_fused", &cw_ctx::map_weft_fused, 0, 1},
     {"map_insert_wave", &cw_ctx::map_insert_wave, 0, 1},
     {"invert_cap", &cw_ctx::invert_cap, 1, 4096},
+    {"transact_cap", &cw_ctx::transact_cap, 1, 4096},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"list_weft_fused", &cw_ctx::list_weft_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
@@ -7878,6 +7889,12 @@ int cw_render_bases(cw_ctx *c, const cw_render_bases_batch *b, cw_render_bases_r
   if (!c) return -1;
   c->err.clear();
   return render_bases_impl(c, b, r, memspace);
+}
+
+int cw_transact(cw_ctx *c, const cw_transact_batch *b, cw_transact_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return transact_impl(c, b, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,
