@@ -13,7 +13,7 @@ GENLIB  := cause_amd/libcauseweave_gen.so
 ORACLE  := oracle/liboracle.so
 
 HIP_SRC := cause_amd/csrc/causeweave.hip
-HIP_HDR := include/causeweave.h include/causeweave_insert.h include/causeweave_map_insert.h include/causeweave_invert.h include/causeweave_render_bases.h include/causeweave_transact.h cause_amd/csrc/cw_internal.h cause_amd/csrc/lookback.h cause_amd/csrc/xplan.h cause_amd/csrc/exact.hip cause_amd/csrc/k128.hip cause_amd/csrc/mappack.hip cause_amd/csrc/mapmerge.hip cause_amd/csrc/mapweft.hip cause_amd/csrc/mapinsert.hip cause_amd/csrc/listmerge.hip cause_amd/csrc/listweft.hip cause_amd/csrc/render.hip cause_amd/csrc/listinsert.hip cause_amd/csrc/invert.hip cause_amd/csrc/renderbase.hip cause_amd/csrc/transact.hip cause_amd/csrc/dist.hip cause_amd/csrc/onesweep.hip
+HIP_HDR := include/causeweave.h include/causeweave_insert.h include/causeweave_map_insert.h include/causeweave_invert.h include/causeweave_render_bases.h include/causeweave_transact.h include/causeweave_sync.h cause_amd/csrc/cw_internal.h cause_amd/csrc/lookback.h cause_amd/csrc/xplan.h cause_amd/csrc/sync_plan.h cause_amd/csrc/exact.hip cause_amd/csrc/k128.hip cause_amd/csrc/mappack.hip cause_amd/csrc/mapmerge.hip cause_amd/csrc/mapweft.hip cause_amd/csrc/mapinsert.hip cause_amd/csrc/listmerge.hip cause_amd/csrc/listweft.hip cause_amd/csrc/sync.hip cause_amd/csrc/render.hip cause_amd/csrc/listinsert.hip cause_amd/csrc/invert.hip cause_amd/csrc/renderbase.hip cause_amd/csrc/transact.hip cause_amd/csrc/dist.hip cause_amd/csrc/onesweep.hip
 
 all: $(LIB) $(GENLIB) $(ORACLE)
 

@@ -18,6 +18,9 @@ order equals the full reweave).  There is no CPU weave in this module.
                                                     -> list_weave_node / insert_lists (cw_insert_lists)
     map.cljc:29-45        weave 2/3-arity, incremental (s/weave-node on one key weave)
                                                     -> map_weave_node / insert_maps (cw_insert_maps)
+    shared.cljc:96-108    (peek yarn) of every yarn -> versions (cw_version)
+    shared.cljc:295-299   the diff merge-trees asks for
+                                                    -> deltas / sync_lists / sync_maps (cw_delta)
     list.cljc:36-43       conj- / cons-             -> list_conj / list_cons
     list.cljc:48-72       hide? / ->edn / ->list    -> causal_list_to_edn / _to_list
 """
@@ -28,7 +31,7 @@ import threading
 
 import numpy as np
 
-from . import abi, abi_insert, abi_map_insert, pack
+from . import abi, abi_insert, abi_map_insert, abi_sync, pack
 
 
 class Keyword:
@@ -333,9 +336,15 @@ def merge_lists(pairs):
     off_b[1:] = np.cumsum([len(b) for b in db])
     side = lambda idx, off: (off, pk.id_key[idx], pk.cause_key[idx], pk.kind[idx], vals[idx])
     res = weaver().merge_lists(side(ia, off_a), side(ib, off_b), pk.layout)
+    return _merged_lists(res, [ct1 for ct1, _ in pairs], da, db)
+
+
+def _merged_lists(res, firsts, da, db):
+    """The merged cts of a cw_merge_lists result: document d is firsts[d] with
+    the nodes da[d] (side a) and db[d] (side b)."""
     vis = res.weave.visible()
     out = []
-    for d, ((ct1, ct2), a, b) in enumerate(zip(pairs, da, db)):
+    for d, (ct1, a, b) in enumerate(zip(firsts, da, db)):
         st = int(res.weave.status[d])
         if st & abi.STATUS_DUP:
             raise CauseError("This node is already in the tree and can't be changed.",
@@ -617,9 +626,16 @@ def merge_maps(pairs):
     side = lambda idx, off: (off, pm.id_key[idx], pm.cause[idx], pm.cause_is_id[idx], pm.kind[idx],
                              vals[idx])
     res = weaver().merge_maps(side(ia, off_a), side(ib, off_b), pm.token_bits, pm.layout.key_bits)
+    return _merged_maps(res, [ct1 for ct1, _ in pairs], da, db, pm, range(len(pairs)))
+
+
+def _merged_maps(res, firsts, da, db, pm, packed_as):
+    """The merged cts of a cw_merge_maps result: collection d is firsts[d] with
+    the nodes da[d] (side a) and db[d] (side b), packed as pm's collection
+    packed_as[d] (its site ranks)."""
     segs_of = _segs_by_coll(res.maps)
     out = []
-    for d, ((ct1, ct2), a, b) in enumerate(zip(pairs, da, db)):
+    for d, (ct1, a, b) in enumerate(zip(firsts, da, db)):
         st = int(res.maps.status[d])
         if st & abi.STATUS_DUP:
             raise CauseError("This node is already in the tree and can't be changed.",
@@ -633,7 +649,7 @@ def merge_maps(pairs):
         merged = [a[s] if s < len(a) else b[s - len(a)] for s in src.tolist()]
         new = dict(ct1)
         new["nodes"] = {n[0]: (n[1], n[2]) for n in merged}
-        new["weave"], new["_active"] = _key_weaves(res.maps, segs_of.get(d, []), merged, pm, d)
+        new["weave"], new["_active"] = _key_weaves(res.maps, segs_of.get(d, []), merged, pm, packed_as[d])
         # insert fast-forwards ::lamport-ts to every newly inserted node (shared.cljc:179-181)
         fresh = [merged[i][0][0] for i, s in enumerate(src.tolist()) if s >= len(a)]
         new["lamport_ts"] = max([ct1["lamport_ts"]] + fresh)
@@ -877,3 +893,165 @@ def maps_to_edn(cts):
 def causal_map_to_list(ct):
     """map.cljc:105-109"""
     return [n for n in ct["_active"].values() if n is not BLANK]
+
+
+# ------------------------------------------------ versions, deltas and syncing ----
+def _pack_ids(cts, extra_ids=None):
+    """The ids of list and map cts alike under one layout (only ids decide what
+    cw_version / cw_delta compute); every document gets its own site ranking."""
+    docs = [[(i, None, None) for i in ct["nodes"]] for ct in cts]
+    return pack.pack_lists(docs, min_site_bits=1, extra_ids=extra_ids)
+
+
+def versions(cts):
+    """The version vector of many cts (lists and maps may be mixed) in ONE GPU
+    call (cw_version): per ct a dict {site_id: id}, the newest id of each site,
+    ``(first (peek yarn))`` of every yarn of s/spin (shared.cljc:96-108).  The
+    root's own yarn ("0") is left out: its only id is the root id, which no weft
+    and no delta names."""
+    pk = _pack_ids(cts)
+    lay = pk.layout
+    S = 1 << lay.site_bits
+    res = abi_sync.version(weaver(), pk.offsets, pk.id_key, lay)
+    out = []
+    for d, pd in enumerate(pk.docs):
+        row = res.ver[d * S:(d + 1) * S].tolist()
+        ids = (_unpack_id(w, lay, pd.site_rank) for w in row if w)
+        out.append({i[1]: i for i in ids if i != ROOT_ID})
+    return out
+
+
+def _have_table(pk, vers):
+    """A version dict per document of pk as the have table of cw_delta."""
+    lay = pk.layout
+    S = 1 << lay.site_bits
+    have = np.zeros(len(pk.docs) << lay.site_bits, np.uint64)
+    for d, (pd, ver) in enumerate(zip(pk.docs, vers)):
+        for site, i in ver.items():
+            if i != ROOT_ID:
+                have[d * S + pd.site_rank[site]] = lay.pack(i[0], pd.site_rank[site], i[2])
+    return have
+
+
+def deltas(items):
+    """What a peer lacks, for many (ct, version) items in ONE GPU call
+    (cw_delta): ``version`` is the peer's version vector as ``versions`` returns
+    it ({site_id: id}; a site it does not name: the peer has nothing of it).
+    Per item the nodes ``(id, cause, value)`` of ct whose id is above the peer's
+    head of their site, in id order: the complement of what s/weft
+    (shared.cljc:268-293) keeps at that version.  Lists and maps may be mixed."""
+    cts = [ct for ct, _ in items]
+    pk = _pack_ids(cts, extra_ids=[[i for i in v.values() if i != ROOT_ID] for _, v in items])
+    have = _have_table(pk, [v for _, v in items])
+    res = abi_sync.delta(weaver(), pk.offsets, pk.id_key, None, None, None, pk.layout, have)
+    out = []
+    for d, (ct, pd) in enumerate(zip(cts, pk.docs)):
+        lo, hi = int(res.delta_offsets[d]), int(res.delta_offsets[d + 1])
+        order = np.argsort(res.delta_id[lo:hi], kind="stable")
+        ids = [pd.nodes[int(s)][0] for s in res.delta_src[lo:hi][order]]
+        out.append([(i,) + tuple(ct["nodes"][i]) for i in ids])
+    return out
+
+
+def _sync_deltas(offsets, id_key, cause, kind, cause_is_id, layout):
+    """Both replicas of every pair as one batch (documents 2d and 2d + 1): the
+    versions of all, then per document the nodes above the OTHER replica's
+    heads.  -> the cw_delta result (delta_src: indices into the document)."""
+    w = weaver()
+    ver = abi_sync.version(w, offsets, id_key, layout).ver
+    have = ver.reshape((len(offsets) - 1) // 2, 2, 1 << layout.site_bits)[:, ::-1].reshape(-1)
+    return abi_sync.delta(w, offsets, id_key, cause, kind, cause_is_id, layout, have)
+
+
+def _sync_offsets(da, db):
+    """The offsets of the batch in which document 2d is replica 1 of pair d and
+    document 2d + 1 replica 2: the arrays of the pairs packed as a + b, split."""
+    off2 = np.zeros(2 * len(da) + 1, np.uint64)
+    off2[1:] = np.cumsum([n for a, b in zip(da, db) for n in (len(a), len(b))])
+    return off2
+
+
+def _other_side(res, off2):
+    """cw_delta's documents with every two neighbours swapped: side b of the
+    merge.  -> (offsets, where each side-b node stands in the delta columns,
+    its index in the batch the delta was taken of)."""
+    do = res.delta_offsets.astype(np.int64)
+    D = len(do) - 1
+    swap = [d ^ 1 for d in range(D)]
+    off_b = np.zeros(D + 1, np.uint64)
+    off_b[1:] = np.cumsum([do[k + 1] - do[k] for k in swap])
+    at = np.concatenate([np.zeros(0, np.int64)] + [np.arange(do[k], do[k + 1]) for k in swap])
+    first = np.repeat(off2[:-1].astype(np.int64), np.diff(do))  # of each delta node's document
+    return off_b, at, (first + res.delta_src.astype(np.int64))[at]
+
+
+def _sync(pairs, both, is_map):
+    """sync_lists / sync_maps: the versions of both replicas of every pair, the
+    deltas both ways, ONE merge call in which document 2d is replica 1 with
+    replica 2's delta and document 2d + 1 the reverse."""
+    for ct1, ct2 in pairs:
+        if ct1["type"] != ct2["type"]:
+            raise CauseError("Causal type missmatch. Merge not allowed.", {"type-missmatch"})
+        if ct1["uuid"] != ct2["uuid"]:
+            raise CauseError("Causal UUID missmatch. Merge not allowed.", {"uuid-missmatch"})
+    da = [[(i, b[0], b[1]) for i, b in ct1["nodes"].items()] for ct1, _ in pairs]
+    db = [[(i, b[0], b[1]) for i, b in ct2["nodes"].items()] for _, ct2 in pairs]
+    both_sides = [a + b for a, b in zip(da, db)]  # one site ranking (and key-token table) per pair
+    if is_map:
+        pk = pack.pack_maps(both_sides, min_site_bits=1)
+        nodes = [n for d in pk.docs for n in d]
+        cols = (pk.id_key, pk.cause, pk.cause_is_id, pk.kind)
+        res = _sync_deltas((off2 := _sync_offsets(da, db)), pk.id_key, pk.cause, pk.kind, pk.cause_is_id, pk.layout)
+        gathered = (res.delta_id, res.delta_cause, res.delta_cause_is_id, res.delta_kind)
+    else:
+        pk = pack.pack_lists(both_sides, min_site_bits=1)
+        nodes = [n for d in pk.docs for n in d.nodes]
+        cols = (pk.id_key, pk.cause_key, pk.kind)
+        res = _sync_deltas((off2 := _sync_offsets(da, db)), pk.id_key, pk.cause_key, pk.kind, None, pk.layout)
+        gathered = (res.delta_id, res.delta_cause, res.delta_kind)
+    off_b, at, ib = _other_side(res, off2)
+    tok = _Tokens()
+    vals = np.array([tok(n[2]) for n in nodes], np.uint64)
+    side_a = (off2,) + cols + (vals,)
+    side_b = (off_b,) + tuple(c[at] for c in gathered) + (vals[ib],)
+    firsts = [ct for pair in pairs for ct in pair]
+    la = [x for a, b in zip(da, db) for x in (a, b)]
+    lb = [[nodes[int(g)] for g in ib[int(off_b[k]):int(off_b[k + 1])]] for k in range(2 * len(pairs))]
+    if is_map:
+        m = weaver().merge_maps(side_a, side_b, pk.token_bits, pk.layout.key_bits)
+        out = _merged_maps(m, firsts, la, lb, pk, [k // 2 for k in range(2 * len(pairs))])
+    else:
+        m = weaver().merge_lists(side_a, side_b, pk.layout)
+        out = _merged_lists(m, firsts, la, lb)
+    return [(out[2 * d], out[2 * d + 1]) for d in range(len(pairs))] if both else out[::2]
+
+
+def sync_lists(pairs, both=False):
+    """s/merge-trees (shared.cljc:300-314) for many (ct1, ct2) list pairs by
+    way of the diff its own comment asks for (shared.cljc:295-299): both
+    replicas of every pair packed under one layout, the versions of both
+    (cw_version), the deltas both ways (cw_delta), and each replica merged with
+    only the other's delta (ONE cw_merge_lists call).  Per pair the merged ct,
+    the value ``merge_lists(pairs)`` returns; both=True: (ct1 merged, ct2
+    merged).
+
+    Precondition: each replica holds a PREFIX of every yarn -- if it has a node
+    of a site it has every older node of that site.  That is what s/insert's
+    cause-must-exist check (shared.cljc:151-184) and a Lamport clock give
+    replicas that only ever append and merge.  Then the nodes above the other
+    side's heads are exactly the nodes it lacks.  For arbitrary node bags
+    ``merge_lists`` is the call to use."""
+    return _sync(pairs, both, False)
+
+
+def sync_maps(pairs, both=False):
+    """CausalMap's causal-merge (map.cljc:248-249) for many (ct1, ct2) map pairs
+    by way of versions and deltas, as ``sync_lists``: ONE cw_version, ONE
+    cw_delta and ONE cw_merge_maps call in which each replica meets only the
+    other's delta.  Per pair the merged ct, the value ``merge_maps(pairs)``
+    returns; both=True: (ct1 merged, ct2 merged).
+
+    Precondition: as ``sync_lists``: each replica holds a prefix of every yarn
+    (s/insert's cause-must-exist and a Lamport clock give that); for arbitrary
+    node bags ``merge_maps`` is the call to use."""
+    return _sync(pairs, both, True)

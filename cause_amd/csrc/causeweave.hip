@@ -47,9 +47,11 @@
 #include "causeweave_invert.h"
 #include "causeweave_render_bases.h"
 #include "causeweave_transact.h"
+#include "causeweave_sync.h"
 #include "cw_internal.h"
 #include "lookback.h"
 #include "xplan.h"
+#include "sync_plan.h"
 
 using namespace cw;
 
@@ -4555,6 +4557,12 @@ struct cw_ctx {
     size_t pin_bytes = 0;
   } transact;
   uint32_t transact_cap = 4096;    // transact_cap: most tokens of a base that cw_transact sorts in LDS
+  uint32_t sync_wave = 1;          // sync_wave: a wave per small document in cw_version / cw_delta (0: a workgroup)
+  uint32_t sync_fused = 1;         // sync_fused: the one-kernel routes of cw_version / cw_delta (0: tiled / general)
+  struct Sync {                    // cw_version / cw_delta (sync.hip)
+    DevLayout docs;                // doc_offsets
+    LookBack lb;                   // k_sync_delta's look-back words
+  } sync;
 };
 
 namespace {
@@ -6311,6 +6319,7 @@ int weave_lists_device(cw_ctx *c, const cw_list_batch *bt, const uint64_t *id_ke
 #include "mapinsert.hip"
 #include "listmerge.hip"
 #include "listweft.hip"
+#include "sync.hip"
 #include "render.hip"
 #include "listinsert.hip"
 #include "invert.hip"
@@ -7736,6 +7745,8 @@ static const struct {
     {"transact_cap", &cw_ctx::transact_cap, 1, 4096},
     {"list_merge_fused", &cw_ctx::list_merge_fused, 0, 1},
     {"list_weft_fused", &cw_ctx::list_weft_fused, 0, 1},
+    {"sync_wave", &cw_ctx::sync_wave, 0, 1},
+    {"sync_fused", &cw_ctx::sync_fused, 0, 1},
     {"xfold", &cw_ctx::xfold, 0, UINT32_MAX},
     {"x_round_cap", &cw_ctx::x_round_cap, 1, UINT32_MAX},
 };
@@ -7895,6 +7906,18 @@ int cw_transact(cw_ctx *c, const cw_transact_batch *b, cw_transact_result *r, in
   if (!c) return -1;
   c->err.clear();
   return transact_impl(c, b, r, memspace);
+}
+
+int cw_version(cw_ctx *c, const cw_sync_batch *b, cw_version_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return version_impl(c, b, r, memspace);
+}
+
+int cw_delta(cw_ctx *c, const cw_sync_batch *b, const uint64_t *have, cw_delta_result *r, int memspace) {
+  if (!c) return -1;
+  c->err.clear();
+  return delta_impl(c, b, have, r, memspace);
 }
 
 int cw_sort_keys(cw_ctx *c, const uint64_t *keys, uint64_t n, uint32_t key_bits, uint64_t *keys_out,
